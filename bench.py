@@ -7,14 +7,24 @@ rank).  Inputs are resident in HBM before the timed region.  Strong scaling: the
 total, sharded contiguously over the ranks.
 
 `value` is the DEPENDENT-step figure (schedule C): theta of step i+1 is computed on the host from the result of step i that
-the host has read (an optimiser step, /root/reference's experiments/snelson/example.py:31-32 semantics), so neither the M-side
+the host has read (an optimiser step, the reference's experiments/snelson/example.py:31-32 semantics), so neither the M-side
 launch nor the host forward pass of step i+1 can start before step i is finished; the only overlap is the theta-free Phi pass
-of step i+1 under the M-side of step i.  The --steps block is timed R times (--repeats) inside the process: `value` /
-`ms_per_step` are the median block, min / max ride along.  Extras: `one_step_at_a_time` (one stream, fixed theta, host runs
-ahead: the device-side latency of a full step) and `independent_evaluations` (several steps with the SAME theta in flight: a
-throughput of independent evaluations, not a step latency).
+of step i+1 under the M-side of step i.
 
-Prints ONE JSON line on rank 0.  python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what `value` needs: set-up, --warmup untimed steps, ONE block of exactly --steps timed steps,
+the outputs (--dump-outputs) and the result line.  --full adds everything else: the --steps block timed R times (--repeats,
+default 11; `value` / `ms_per_step` are then the median block, min / max ride along), HIP events around every n-th Phi kernel,
+the stream ceiling and `roofline`, the CPU baselines and the parity against the oracle, and the extra schedules:
+`one_step_at_a_time` (one stream, fixed theta, host runs ahead: the device-side latency of a full step),
+`independent_evaluations` (several steps with the SAME theta in flight: a throughput of independent evaluations, not a step
+latency), three buffer sets, the all-GPU prior chain, launch-ahead, emulated shards, the other input order, the posterior and
+the Kronecker shape, and weak scaling on N > 1 ranks.
+
+--dump-outputs DIR writes what the timed path returned in its last step as float64 .npy files: elbo.npy (1,), grad.npy (3,:
+d elbo / d (variance, lengthscale, noise variance)) and theta.npy (3,: the point that step evaluated).  The inputs are seeded, so the
+same arguments give the same inputs in every run.
+
+Prints ONE JSON line on rank 0.  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 With --gpus N > 1 and no torchrun environment (RANK unset) the script launches itself: the parent - before any GPU
 call - starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` on this
 file and exits with its return code; under torchrun (RANK set) it is the worker.
@@ -196,7 +206,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=11, help="the --steps block is timed this many times; median / min / max are reported")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond `value` (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None, help="the --steps block is timed this many times; median / min / max are reported "
+                    "(default 1, with --full 11)")
     ap.add_argument("--points", type=int, default=10_000_000)
     ap.add_argument("--features", type=int, default=2048)
     ap.add_argument("--sorted", action="store_true", help="secondary case: time-series (sorted) inputs")
@@ -244,8 +257,9 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    full = args.full
     cpu_all = None
-    if world == 1 and not args.no_cpu_baseline and not args.no_cpu_all_cores:
+    if full and world == 1 and not args.no_cpu_baseline and not args.no_cpu_all_cores:
         cpu_all = cpu_baseline_all_cores(args.points, args.features, args.sorted)   # (before this process touches the GPU)
     torch.cuda.set_device(local_rank % max(torch.cuda.device_count(), 1))
     if world > 1:
@@ -259,7 +273,9 @@ def main():
     lib = _lib.get_lib()
 
     N, M = args.points, args.features
-    K_steps, R = args.steps, max(1, args.repeats)
+    K_steps = args.steps
+    R = max(1, args.repeats if args.repeats is not None else (11 if full else 1))
+    kernel_events = args.kernel_events if full else 0      # (HIP events around Phi launches feed `roofline` only)
     theta0 = (1.0, 0.05, 0.01)
     x, y = synth(N)
     if args.sorted:
@@ -296,12 +312,12 @@ def main():
 
     def timed_blocks(block_fn, h, settle=None):
         """args.warmup untimed steps, then R blocks of EXACTLY K steps, each between barrier + synchronize pairs; max over ranks per block.
-        HIP events around every n-th Phi launch of handle h inside the timed blocks."""
+        HIP events around every n-th Phi launch of handle h inside the timed blocks (--full only)."""
         block_fn(args.warmup)
         if settle:
             settle()
         torch.cuda.synchronize()
-        lib.asvgp_profile_enable(h.ptr, args.kernel_events)
+        lib.asvgp_profile_enable(h.ptr, kernel_events)
         ms = []
         for _ in range(R):
             if world > 1:
@@ -326,59 +342,67 @@ def main():
         lib.asvgp_profile_enable(h.ptr, 0)
         return ms, ms_sum.value / max(launches.value, 1) * 1e3, int(launches.value)
 
-    # ---- stream ceiling: a read-only pass over the same x, y with the Phi pass's launch shape, HIP events per launch
-    sink = torch.zeros(8, dtype=torch.float64, device="cuda")
-    st_main = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    probe_us = []
-    for i in range(23):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(lib.asvgp_stream_probe(xd.data_ptr(), yd.data_ptr(), n_local, sink.data_ptr(), st_main), "stream_probe")
-        e1.record()
-        e1.synchronize()
-        if i >= 3:
-            probe_us.append(e0.elapsed_time(e1) * 1e3)
-    ceiling_us = float(np.median(probe_us))
-    ceiling_gbs = BYTES_PER_POINT * n_local / (ceiling_us * 1e-6) / 1e9
+    # ---- stream ceiling (--full): a read-only pass over the same x, y with the Phi pass's launch shape, HIP events per launch
+    ceiling_us = ceiling_gbs = None
+    if full:
+        sink = torch.zeros(8, dtype=torch.float64, device="cuda")
+        st_main = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        probe_us = []
+        for i in range(23):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(lib.asvgp_stream_probe(xd.data_ptr(), yd.data_ptr(), n_local, sink.data_ptr(), st_main), "stream_probe")
+            e1.record()
+            e1.synchronize()
+            if i >= 3:
+                probe_us.append(e0.elapsed_time(e1) * 1e3)
+        ceiling_us = float(np.median(probe_us))
+        ceiling_gbs = BYTES_PER_POINT * n_local / (ceiling_us * 1e-6) / 1e9
 
-    # ---- schedule A: one step at a time on one stream, theta fixed (the host enqueues ahead): device-side latency of a full step
-    model = new_model(N, overlapped=False)
-    stats = model._stats
-    marks = []
-    n_marks = (args.warmup + K_steps * R) // max(args.phase_events, 1) + 2 if args.phase_events > 0 else 0
-    ev_pool = [torch.cuda.Event(enable_timing=True) for _ in range(4 * n_marks)]   # (made before the timed region; sampled: a record costs stream time)
-    ev = ev_pool.pop
-    count = [0]
+    # ---- schedule A (--full, or when schedule C fails): one step at a time on one stream, theta fixed (the host enqueues ahead):
+    # device-side latency of a full step.  Returns (figures, model): the caller keeps the model alive as long as it wants.
+    def serial_schedule(n_total, phase_events):
+        model = new_model(n_total, overlapped=False)
+        stats = model._stats
+        marks = []
+        n_marks = (args.warmup + K_steps * R) // max(phase_events, 1) + 2 if phase_events > 0 else 0
+        ev_pool = [torch.cuda.Event(enable_timing=True) for _ in range(4 * n_marks)]   # (made before the timed region; sampled: a record costs stream time)
+        ev = ev_pool.pop
+        count = [0]
 
-    def serial_block(k):
-        for _ in range(k):
-            rec = args.phase_events > 0 and count[0] % args.phase_events == 0 and len(ev_pool) >= 4
-            count[0] += 1
-            if rec:
-                e0, e1, e2, e3 = ev(), ev(), ev(), ev()
-                e0.record()
-            model.phi_pass(allreduce=False)
-            if rec:
-                e1.record()
-            if world > 1:
-                dist.all_reduce(stats, op=dist.ReduceOp.SUM)
-            if rec:
-                e2.record()
-            model._launch_elbo()
-            if rec:
-                e3.record()
-                marks.append((e0, e1, e2, e3))
+        def serial_block(k):
+            for _ in range(k):
+                rec = phase_events > 0 and count[0] % phase_events == 0 and len(ev_pool) >= 4
+                count[0] += 1
+                if rec:
+                    e0, e1, e2, e3 = ev(), ev(), ev(), ev()
+                    e0.record()
+                model.phi_pass(allreduce=False)
+                if rec:
+                    e1.record()
+                if world > 1:
+                    dist.all_reduce(stats, op=dist.ReduceOp.SUM)
+                if rec:
+                    e2.record()
+                model._launch_elbo()
+                if rec:
+                    e3.record()
+                    marks.append((e0, e1, e2, e3))
 
-    ser_ms, kern_us, n_launches = timed_blocks(serial_block, model._h)
-    model._check_pd()
-    phi_algo_ran = model._h.phi_last_algorithm()
-    mk = marks[1:] if len(marks) > 1 else marks          # (the first sampled step carries plan creation and allocations: excluded)
-    t_phi = float(np.median([a.elapsed_time(b) for a, b, _, _ in mk]) * 1e3) if mk else 0.0
-    t_comm = float(np.median([b.elapsed_time(c) for _, b, c, _ in mk]) * 1e3) if mk else 0.0
-    t_band = float(np.median([c.elapsed_time(d) for _, _, c, d in mk]) * 1e3) if mk else 0.0
-    phi_order_ran = model._h.phi_last_input_order() if model._h.phi_last_algorithm() == 6 else 0
-    out4 = model._out.cpu().numpy()
-    stats_host = stats.cpu().numpy()
+        ms, kern_us, n_launches = timed_blocks(serial_block, model._h)
+        model._check_pd()
+        mk = marks[1:] if len(marks) > 1 else marks          # (the first sampled step carries plan creation and allocations: excluded)
+        res = {"ms": ms, "kern_us": kern_us, "launches": n_launches, "phi_algo": model._h.phi_last_algorithm(),
+               "phi_order": model._h.phi_last_input_order() if model._h.phi_last_algorithm() == 6 else 0,
+               "t_phi": float(np.median([a.elapsed_time(b) for a, b, _, _ in mk]) * 1e3) if mk else 0.0,
+               "t_comm": float(np.median([b.elapsed_time(c) for _, b, c, _ in mk]) * 1e3) if mk else 0.0,
+               "t_band": float(np.median([c.elapsed_time(d) for _, _, c, d in mk]) * 1e3) if mk else 0.0,
+               "samples": len(mk), "out4": model._out.cpu().numpy(), "stats_host": stats.cpu().numpy(), "n_stats": stats.numel()}
+        return res, model
+
+    ser, ser_model = None, None
+    if full:
+        ser, ser_model = serial_schedule(N, args.phase_events)
 
     # ---- schedule C (`value`): dependent steps.  theta_{i+1} = theta_0 (1 + 1e-6 delta(result_i)) is computed on the host from the result of
     # step i that the host has read, so nothing of step i+1 that needs theta (ELBO launch, host forward pass) can start earlier.  The Phi
@@ -480,8 +504,12 @@ def main():
                 else:
                     r = ln.read_elbo_host(tok)
                 t3 = time.perf_counter()
-                d = (r[0] * 1e3) % 1.0 - 0.5                       # any function of the host-read result; 1e-6 relative keeps the workload
-                state["theta"] = tuple(t * (1.0 + 1e-6 * d) for t in theta0)
+                # theta_{i+1} from the host-read result: a move of at most 5e-7 relative (the workload stays the same) along the sign of
+                # the gradient, its size set by the step index.  The signs sit far above the result's rounding, so every step's theta -
+                # and the last step's outputs - are the same from run to run and from build to build.
+                d = ((i + 1) * 0.6180339887498949) % 1.0 - 0.5
+                state["last_theta"] = state["theta"]
+                state["theta"] = tuple(t * (1.0 + 1e-6 * d * (1.0 if g >= 0.0 else -1.0)) for t, g in zip(theta0, r[1:4]))
                 state["last"] = r
                 state["i"] = i + 1
                 if k == K_steps:                                    # (timed blocks only: the warm-up carries one-time allocations)
@@ -490,7 +518,8 @@ def main():
 
         ms, kern_us, launches = timed_blocks(block, lanes[0]._h)
         n_acc = max(state["n"], 1)
-        out = {"ms": ms, "kern_us": kern_us, "launches": launches, "last": state["last"], "launch_ahead": bool(ahead_ok and state.get("n_ahead", 0) > 0), "ahead_launches": state.get("n_ahead", 0),
+        out = {"ms": ms, "kern_us": kern_us, "launches": launches, "last": state["last"], "last_theta": state["last_theta"], "n_stats": lanes[0]._stats.numel(),
+               "launch_ahead": bool(ahead_ok and state.get("n_ahead", 0) > 0), "ahead_launches": state.get("n_ahead", 0),
                "fallbacks": sum(getattr(ln, "fused_launch_fallbacks", 0) for ln in lanes),
                "host_us": {("phi_kernel_enqueue_theta_and_elbo_launch" if n_sets == 2 else "theta_and_elbo_launch"): state["t_a"] / n_acc * 1e6,
                            ("reduce_and_event_enqueue" if n_sets == 2 else "n_side_enqueue"): state["t_b"] / n_acc * 1e6,
@@ -505,7 +534,7 @@ def main():
         return out
 
     dep, dep_error, dep3, dep3_error = None, None, None, None
-    for n_sets in ((2,) if args.no_three_sets else (2, 3)):
+    for n_sets in ((2, 3) if full and not args.no_three_sets else (2,)):
         try:
             res = dependent_schedule(n_sets, launch_ahead_mode=bool(args.value_launch_ahead) and n_sets == 2)
             if n_sets == 2:
@@ -522,12 +551,14 @@ def main():
                 torch.cuda.synchronize()
             except Exception:
                 pass
+    if dep is None and ser is None:
+        ser, ser_model = serial_schedule(N, args.phase_events if full else 0)
 
     # ---- schedule B (extra): L steps with the SAME theta in flight - a throughput of independent evaluations.  N-side stream: Phi pass of
     # step i+1; M-side streams in turn: reduce, [all-reduce], ELBO launch of steps i, i-1.  Every step is a complete evaluation from the raw
     # points into its own buffers; a lane is reused once the host has seen its previous step finish.
     ind, ind_error = None, None
-    if args.in_flight >= 2:
+    if full and args.in_flight >= 2:
         try:
             lanes = [[new_model(N, overlapped=True), torch.cuda.Event(), torch.cuda.Event(), False] for _ in range(args.in_flight)]
             s_phi = stream_pool["n"]
@@ -558,7 +589,7 @@ def main():
             outs = [ln[0]._out.cpu().numpy() for ln in lanes]
             for ln in lanes:
                 ln[0]._check_pd()
-            ind = {"ms": ind_ms, "max_rel_diff_vs_serial": float(max(np.max(np.abs(o[:4] - out4[:4]) / np.abs(out4[:4])) for o in outs))}
+            ind = {"ms": ind_ms, "max_rel_diff_vs_serial": float(max(np.max(np.abs(o[:4] - ser["out4"][:4]) / np.abs(ser["out4"][:4])) for o in outs))}
             del lanes
         except Exception as exc:
             ind, ind_error = None, repr(exc)[:300]
@@ -571,7 +602,7 @@ def main():
     # double-double (no host arithmetic in the step), and with one rank's share of 2 / 4 / 8 ranks (the first N/2, N/4, N/8 points; world
     # size 1, no collective): what a rank of a strong-scaling run does per step before any collective latency.
     extras = {}
-    if dep is not None and not args.no_extras and world == 1:   # (the extras are rows of the N = 1 line; a multi-rank run keeps to the contract's schedules)
+    if full and dep is not None and not args.no_extras and world == 1:   # (the extras are rows of the N = 1 line; a multi-rank run keeps to the contract's schedules)
         try:
             res = dependent_schedule(2, prior_forward=1)
             mg = new_model(N, overlapped=False, prior_forward=1)
@@ -687,29 +718,27 @@ def main():
     # Extra, N > 1 only: the one-at-a-time step with the BASELINE N on EVERY rank (weak scaling).  `value` stays the strong-scaling figure
     # the metric is quoted on; this field only shows what the replicated band chains cost in the other regime.
     weak = None
-    if world > 1 and not os.environ.get("ASVGP_BENCH_NOWEAK"):
+    if full and world > 1 and not os.environ.get("ASVGP_BENCH_NOWEAK"):
         try:
             xw, yw = synth(N, seed=1234 + rank)
-            del model
+            ser_model = None
             xd = torch.from_numpy(xw).cuda().reshape(-1, 1)
             yd = torch.from_numpy(yw).cuda().reshape(-1, 1)
-            model = new_model(N * world, overlapped=False)
-            stats = model._stats
-            count[0] = 1                                  # (no phase events)
-            pe, args.phase_events = args.phase_events, 0
-            wk_ms, _, _ = timed_blocks(serial_block, model._h)
-            args.phase_events = pe
-            wk = spread(wk_ms)
+            wk_res, ser_model = serial_schedule(N * world, 0)     # (no phase events)
+            wk = spread(wk_res["ms"])
             weak = {"value": N * world / (wk["median"] * 1e-3) / 1e6, "unit": "Mpoints/s", "points_per_rank": N,
                     "ms_per_step": wk, "scaling": "weak", "schedule": "one step at a time"}
         except Exception as exc:   # never let the extra measurement break the contract line
             weak = {"error": repr(exc)[:200]}
 
     if rank == 0:
-        ser = spread(ser_ms)
         mp = lambda ms: N / (ms * 1e-3) / 1e6
-        serial = {"ms_per_step": ser, "value": mp(ser["median"]), "unit": "Mpoints/s", "phi_kernel_us": kern_us,
-                  "schedule": "one stream, theta fixed, the host enqueues ahead: Phi pass -> reduce -> [all-reduce] -> band chains + bound (one launch)"}
+        serial, out4 = None, None
+        if ser is not None:
+            ssp = spread(ser["ms"])
+            out4 = ser["out4"]
+            serial = {"ms_per_step": ssp, "value": mp(ssp["median"]), "unit": "Mpoints/s", "phi_kernel_us": ser["kern_us"],
+                      "schedule": "one stream, theta fixed, the host enqueues ahead: Phi pass -> reduce -> [all-reduce] -> band chains + bound (one launch)"}
         if dep is not None:
             dsp = spread(dep["ms"])
             schedule = ("dependent steps: theta_{i+1} computed on the host from the host-read result of step i (pinned result mirror%s); "
@@ -717,10 +746,8 @@ def main():
                         "second stream under it (host order: Phi kernel of i+1, ELBO launch of i followed by the host's long-double forward pass for it, reduce of i+1); two buffer sets alternate; Phi grid %d workgroups"
                         % (" off: D2H copy + synchronise" if args.no_mirror else "", args.phi_workgroups))
         else:
-            dsp = ser
+            dsp = ssp
             schedule = serial["schedule"] + " (dependent schedule failed: see dependent_schedule_error)"
-        achieved = BYTES_PER_POINT * n_local / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
-        traffic, traffic_src = measured_traffic(n_local, phi_algo_ran, series=(phi_order_ran == 2))
         line = {
             "metric": "Mpoints/s per ELBO+grad step, N=10M 1D Matern-3/2 M=2048",
             "value": mp(dsp["median"]),
@@ -734,31 +761,38 @@ def main():
             "data": "synthetic",
             "config": {"workload": "1D synthetic N=%d (U(0,1) i.i.d. %s), Matern-%d/2, B4Spline(0,1,M=%d) band k=4, theta=(1,0.05,0.01)"
                                    % (N, "sorted" if args.sorted else "unsorted", args.matern // 10, M),
-                       "parallelism": "dp%d (contiguous N-shards, one all-reduce of the %d-double band buffer)" % (world, stats.numel()),
+                       "parallelism": "dp%d (contiguous N-shards, one all-reduce of the %d-double band buffer)" % (world, (dep or ser)["n_stats"]),
                        "points_per_rank": n_local, "schedule": schedule},
             "repeats": {"R": R, "steps_per_block": K_steps, "ms_per_step": dsp, "value_min": mp(dsp["max"]), "value_max": mp(dsp["min"]),
                         "note": "the --steps block timed R times in this process between barrier + synchronize pairs; value / ms_per_step = the median block"},
-            "one_step_at_a_time": serial,
-            "phases_us": {"phi_pass_and_reduce": t_phi, "band_allreduce": t_comm, "elbo_and_gradient_launch": t_band,
-                          "samples": len(mk),
-                          "note": "t_phi / t_comm / t_band of SURVEY 8d: HIP events in the one-step-at-a-time schedule, sampled every %d-th step; "
-                                  "median, first sample (plan creation, allocations) excluded" % args.phase_events},
-            "roofline": {"bound": "hbm", "kernel": PHI_KERNEL_NAMES.get(62 if (phi_algo_ran == 6 and phi_order_ran == 2) else phi_algo_ran, "Phi pass, algorithm %d" % phi_algo_ran), "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "stream_ceiling": {"achieved": ceiling_gbs, "unit": "GB/s", "us": ceiling_us, "frac_of_peak": ceiling_gbs / HBM_PEAK_GBS,
-                                            "kernel": "stream_probe_kernel: read-only 16 B/point over the same x, y, 256 x 1024 threads, non-temporal "
-                                                      "16-byte loads (asvgp_stream_probe), median of 20 launches in this run"},
-                         "frac_of_stream_ceiling": (achieved / ceiling_gbs) if ceiling_gbs > 0 else None,
-                         "kernel_us": kern_us, "launches": n_launches, "algorithmic_bytes_per_launch": BYTES_PER_POINT * n_local,
-                         "kernel_us_in_dependent_schedule": (dep["kern_us"] if dep else None),
-                         "note": "HIP events around every %d-th launch inside the timed one-step-at-a-time blocks (the kernel alone on the device: its own "
-                                 "duration, as in rocprofv3's kernel trace); in the dependent schedule the same events also contain the launch's wait "
-                                 "for CUs next to the chain workgroups" % args.kernel_events},
-            "elbo": float(out4[0]), "grad": [float(v) for v in out4[1:4]],
         }
+        if serial is not None:
+            line["one_step_at_a_time"] = serial
+        if full:
+            kern_us, phi_algo_ran, phi_order_ran = ser["kern_us"], ser["phi_algo"], ser["phi_order"]
+            achieved = BYTES_PER_POINT * n_local / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
+            traffic, traffic_src = measured_traffic(n_local, phi_algo_ran, series=(phi_order_ran == 2))
+            line["phases_us"] = {"phi_pass_and_reduce": ser["t_phi"], "band_allreduce": ser["t_comm"], "elbo_and_gradient_launch": ser["t_band"],
+                                 "samples": ser["samples"],
+                                 "note": "t_phi / t_comm / t_band of SURVEY 8d: HIP events in the one-step-at-a-time schedule, sampled every %d-th step; "
+                                         "median, first sample (plan creation, allocations) excluded" % args.phase_events}
+            line["roofline"] = {"bound": "hbm", "kernel": PHI_KERNEL_NAMES.get(62 if (phi_algo_ran == 6 and phi_order_ran == 2) else phi_algo_ran, "Phi pass, algorithm %d" % phi_algo_ran), "achieved": achieved,
+                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                                "stream_ceiling": {"achieved": ceiling_gbs, "unit": "GB/s", "us": ceiling_us, "frac_of_peak": ceiling_gbs / HBM_PEAK_GBS,
+                                                   "kernel": "stream_probe_kernel: read-only 16 B/point over the same x, y, 256 x 1024 threads, non-temporal "
+                                                             "16-byte loads (asvgp_stream_probe), median of 20 launches in this run"},
+                                "frac_of_stream_ceiling": (achieved / ceiling_gbs) if ceiling_gbs > 0 else None,
+                                "kernel_us": kern_us, "launches": ser["launches"], "algorithmic_bytes_per_launch": BYTES_PER_POINT * n_local,
+                                "kernel_us_in_dependent_schedule": (dep["kern_us"] if dep else None),
+                                "note": "HIP events around every %d-th launch inside the timed one-step-at-a-time blocks (the kernel alone on the device: its own "
+                                        "duration, as in rocprofv3's kernel trace); in the dependent schedule the same events also contain the launch's wait "
+                                        "for CUs next to the chain workgroups" % args.kernel_events}
+        if out4 is not None:
+            line["elbo"], line["grad"] = float(out4[0]), [float(v) for v in out4[1:4]]
         if dep is not None:
-            line["dependent_schedule"] = {"host_us_per_step": dep["host_us"], "fused_launch_fallbacks": dep["fallbacks"],
-                                          "last_result": dep["last"], "rel_diff_elbo_vs_fixed_theta": abs(dep["last"][0] - out4[0]) / abs(out4[0])}
+            line["dependent_schedule"] = {"host_us_per_step": dep["host_us"], "fused_launch_fallbacks": dep["fallbacks"], "last_result": dep["last"]}
+            if out4 is not None:
+                line["dependent_schedule"]["rel_diff_elbo_vs_fixed_theta"] = abs(dep["last"][0] - out4[0]) / abs(out4[0])
         if dep_error is not None:
             line["dependent_schedule_error"] = dep_error
         if dep3 is not None:
@@ -819,11 +853,11 @@ def main():
             line["independent_evaluations_error"] = ind_error
         if weak is not None:
             line["weak_scaling_extra"] = weak
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             ns = min(args.cpu_sample, N)
-            full = (ns == N)
+            whole = (ns == N)
             okind = {12: 0, 32: 1, 52: 2}[args.matern]
-            line["cpu_baseline"], parity = cpu_baseline(x[:ns], y[:ns], M, theta0, okind, stats_host if full else None, out4 if full else None)
+            line["cpu_baseline"], parity = cpu_baseline(x[:ns], y[:ns], M, theta0, okind, ser["stats_host"] if whole else None, out4 if whole else None)
             line["cpu_baseline"]["host"] = host_description()
             if cpu_all is not None:
                 line["cpu_baseline"]["all_cores"] = cpu_all
@@ -834,6 +868,12 @@ def main():
                     line["dependent_steps_all_gpu"]["parity"] = {"abs_elbo_vs_long_double": abs(eg[0] - ee), "rel_elbo_vs_long_double": abs(eg[0] - ee) / abs(ee),
                                                                  "gate": "|ELBO - long double| <= 1e-9 |ELBO|"}
                 line["parity"] = parity
+        if args.dump_outputs:
+            # what the timed path returned in its last step (the dependent schedule; the one-at-a-time schedule when it failed)
+            last, last_theta = (dep["last"], dep["last_theta"]) if dep is not None else (out4[:4], theta0)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in (("elbo", last[:1]), ("grad", last[1:4]), ("theta", last_theta)):
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

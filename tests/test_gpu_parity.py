@@ -1819,7 +1819,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     env["ASVGP_BENCH_BACKEND"] = "gloo"
     env["ASVGP_BENCH_NOWEAK"] = "1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--points", "400000", "--features", "512"], env=env, capture_output=True, text=True, timeout=600)
+                        "--points", "400000", "--features", "512", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

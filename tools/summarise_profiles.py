@@ -67,7 +67,7 @@ if kt:
         if KERNEL in row["Kernel_Name"]:
             wgs = int(row["Grid_Size_X"]) // max(int(row["Workgroup_Size_X"]), 1)
             by_grid.setdefault(wgs, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
-    json.dump({"kernel": KERNEL, "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 30 --warmup 3 --repeats 5 --no-cpu-baseline --no-extras",
+    json.dump({"kernel": KERNEL, "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 30 --warmup 3 --repeats 5 --no-cpu-baseline --no-extras",
                "launches_by_workgroups": {str(k): {"launches": len(v), "average_us": sum(v) / len(v), "min_us": min(v), "max_us": max(v)}
                                           for k, v in sorted(by_grid.items())},
                "note": "256 workgroups = one-step-at-a-time schedule (and warm-up / construction): compare with roofline.kernel_us; 240 = dependent and "

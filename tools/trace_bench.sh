@@ -3,7 +3,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_bench; rm -rf $O; mkdir -p $O; cd $R
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -- python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/err.txt || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -- python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/err.txt || exit 1
 python3 - <<PY
 import csv, glob, json
 f = sorted(glob.glob("$O/t/*/*_kernel_stats.csv"))[-1]
