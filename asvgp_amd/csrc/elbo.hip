@@ -76,6 +76,13 @@ template <int K> struct PostLauncher {
   static int run(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
                  double* alpha, double* W, int* info, void* ws, hipStream_t st);
 };
+// the posterior chain, then the whole of P^-1 - Kuu^-1 (asvgp_posterior_cov_prepare_1d).  Its scratch follows the ELBO workspace:
+// Kuu, P, L_K, L_P bands, the two reciprocal diagonals and two info slots of the plain band Cholesky factorisations.
+static size_t cov_ws_doubles(long M, int k) { return (size_t)4 * (k + 1) * M + (size_t)2 * M + 8; }
+template <int K> struct PostCovLauncher {
+  static int run(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
+                 double* alpha, double* W, double* Wd, int* info, void* ws, hipStream_t st);
+};
 
 #ifdef ASVGP_ELBO_ONLY_K
 struct KuuCoefs2 { double c[ASVGP_MAX_KUU_TERMS]; double dc[ASVGP_MAX_KUU_TERMS]; int n; };
@@ -1094,6 +1101,129 @@ int PostLauncher<K>::run(Handle* h, const double* stats, const double* S, int ki
   }
 }
 
+#if !defined(ASVGP_ELBO_PART) || ASVGP_ELBO_PART == 2
+// ---- the dense W = P^-1 - Kuu^-1 (asvgp_posterior_cov_prepare_1d)
+// 1 / L[j, j] of both factors once, and the plain factorisations' failures folded into the chain's info (a chain failure stays first)
+static __global__ void cov_recip_kernel(const double* __restrict__ LK, const double* __restrict__ LP, long M, double* __restrict__ rK,
+                                        double* __restrict__ rP, const int* __restrict__ finfo, int* __restrict__ info) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < M) { rK[j] = 1.0 / LK[j]; rP[j] = 1.0 / LP[j]; }
+  if (j < 2 && info[j] == 0 && finfo[j] != 0) info[j] = finfo[j];
+}
+
+// Off-band entries of S = A^-1 from its band and L = chol(A).  S L = L^-T is upper triangular, so for i > j
+//   S[i, j] = -(1 / L[j, j]) sum_{l=1..K} L[j+l, j] S[i, j+l]
+// - back substitution with L^T along row i, seeded by the row's own K band entries S[i, i-K .. i-1]; every row is independent.
+// One wave per 64 consecutive rows i, stepping down the columns j together: column j of L is then uniform across the wave, staged through
+// the LDS 64 columns at a time (the next block's loads in flight under the current block's steps); the K and P chains run interleaved in
+// each lane, and the term of the value just formed (l = 1) is added last.  Step j stores W[i, j] = S_P[i, j] - S_K[i, j] of the wave's 64
+// rows as the 64 contiguous doubles W_dense[j, i0 .. i0 + 63] (symmetry): the upper triangle, band and diagonal included - the band entries
+// are the chain's W, bit for bit.  cov_mirror_kernel writes the lower triangle.
+constexpr int COV_CH = 64;
+template <int K>
+__global__ __launch_bounds__(64) void cov_rows_kernel(const double* __restrict__ LK, const double* __restrict__ LP, const double* __restrict__ rK,
+                                                      const double* __restrict__ rP, const double* __restrict__ SK, const double* __restrict__ SP,
+                                                      const double* __restrict__ Wb, int M, double* __restrict__ Wd) {
+  constexpr int NV = 2 * K + 2;           // per column j: L_K[j+1 .. j+K, j], L_P[j+1 .. j+K, j], 1 / L_K[j, j], 1 / L_P[j, j]
+  __shared__ double tab[COV_CH][NV];
+  const int lane = threadIdx.x;
+  const int i0 = blockIdx.x * COV_CH;
+  const int i = i0 + lane;
+  const bool live = i < M;
+  const int jtop = (i0 + COV_CH - 1 < M - 1) ? i0 + COV_CH - 1 : M - 1;
+  double wk[K], wp[K];                    // wk[l - 1] = S_K[i, j + l] at step j
+#pragma unroll
+  for (int l = 0; l < K; ++l) wk[l] = wp[l] = 0.0;
+  double nxt[NV];
+  auto fetch = [&](int jhi) {             // lane c: column jhi - c (the block's columns, coalesced)
+    const int j = jhi - lane;
+    if (j >= 0) {
+#pragma unroll
+      for (int l = 1; l <= K; ++l) { nxt[l - 1] = LK[(long)l * M + j]; nxt[K + l - 1] = LP[(long)l * M + j]; }
+      nxt[2 * K] = rK[j];
+      nxt[2 * K + 1] = rP[j];
+    }
+  };
+  fetch(jtop);
+  for (int jhi = jtop; jhi >= 0; jhi -= COV_CH) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) tab[lane][v] = nxt[v];
+    __syncthreads();
+    if (jhi - COV_CH >= 0) fetch(jhi - COV_CH);
+    const int nj = jhi + 1 < COV_CH ? jhi + 1 : COV_CH;
+    for (int c = 0; c < nj; ++c) {
+      const int j = jhi - c;
+      const int d = i - j;
+      double sk = 0.0, sp = 0.0;
+      if (live && d > K) {
+        double ak = 0.0, ap = 0.0;
+#pragma unroll
+        for (int l = K; l >= 1; --l) { ak = fma(tab[c][l - 1], wk[l - 1], ak); ap = fma(tab[c][K + l - 1], wp[l - 1], ap); }
+        sk = -ak * tab[c][2 * K];
+        sp = -ap * tab[c][2 * K + 1];
+        Wd[(long)j * M + i] = sp - sk;
+      } else if (live && d >= 0) {        // the band: seeds, and the chain's W as it is
+        sk = SK[(long)d * M + j];
+        sp = SP[(long)d * M + j];
+        Wd[(long)j * M + i] = Wb[(long)d * M + j];
+      }
+#pragma unroll
+      for (int l = K - 1; l >= 1; --l) { wk[l] = wk[l - 1]; wp[l] = wp[l - 1]; }
+      wk[0] = sk;
+      wp[0] = sp;
+    }
+    __syncthreads();
+  }
+}
+
+// W_dense[i, j] = W_dense[j, i] for i > j: one 64 x 64 tile of the lower triangle per workgroup, read from the upper one through the LDS
+// (coalesced both ways).  A diagonal tile reads its upper part and writes its lower part only.
+static __global__ __launch_bounds__(256) void cov_mirror_kernel(double* __restrict__ Wd, int M) {
+  const int bi = blockIdx.y, bj = blockIdx.x;   // destination: rows of tile bi, columns of tile bj
+  if (bj > bi) return;
+  __shared__ double t[64][65];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int r = ty; r < 64; r += 4) {
+    const int j = bj * 64 + r, i = bi * 64 + tx;
+    if (i < M && j <= i) t[r][tx] = Wd[(long)j * M + i];
+  }
+  __syncthreads();
+  for (int r = ty; r < 64; r += 4) {
+    const int i = bi * 64 + r, j = bj * 64 + tx;
+    if (i < M && j < i) Wd[(long)i * M + j] = t[tx][r];
+  }
+}
+
+template <int K>
+int PostCovLauncher<K>::run(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
+                            double* alpha, double* W, double* Wd, int* info, void* ws, hipStream_t st) {
+  int rc = PostLauncher<K>::run(h, stats, S, kind, v, l, s, M, D, alpha, W, info, ws, st);
+  if (rc) return rc;
+  // the chains leave band(Kuu^-1) and band(P^-1) in the workspace but not the plain factors: Kuu and P as the chains form them
+  // (elbo_prepare_kernel), then the band Cholesky operator (band_ops.hip) on each
+  const Ws w = carve(ws, M, K, D);
+  const long E = (long)(K + 1) * M;
+  double* c = static_cast<double*>(ws) + ws_doubles(M, K, D);
+  double *Kb = c, *Pb = c + E, *LKb = c + 2 * E, *LPb = c + 3 * E, *rK = c + 4 * E, *rP = rK + M;
+  int* finfo = reinterpret_cast<int*>(rP + M);
+  KuuCoefs2 cf;
+  for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) cf.c[t] = cf.dc[t] = 0.0;
+  rc = asvgp_matern_coeffs(kind, v, l, cf.c, cf.dc, &cf.n);
+  if (rc) return rc;
+  hipLaunchKernelGGL(elbo_prepare_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, S, cf, E, stats, s, Kb, (double*)nullptr, Pb);
+  rc = asvgp_cholesky_band(Kb, LKb, M, K, finfo, st);
+  if (rc) return rc;
+  rc = asvgp_cholesky_band(Pb, LPb, M, K, finfo + 1, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(cov_recip_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, LKb, LPb, M, rK, rP, finfo, info);
+  hipLaunchKernelGGL(cov_rows_kernel<K>, dim3((unsigned)((M + COV_CH - 1) / COV_CH)), dim3(COV_CH), 0, st, LKb, LPb, rK, rP, w.SK, w.SP, W,
+                     (int)M, Wd);
+  const unsigned nt = (unsigned)((M + 63) / 64);
+  hipLaunchKernelGGL(cov_mirror_kernel, dim3(nt, nt), dim3(256), 0, st, Wd, (int)M);
+  return check_launch("posterior_cov_prepare_1d");
+}
+#endif
+
 
 // ---- band(Kuu^-1) with its lengthscale tangent as an operator of its own (asvgp_kuu_inverse_band_1d): the planned chain when the
 // handle holds a plan, else the all-GPU Dual chain (block cyclic reduction when it fits the LDS, sequential sweeps otherwise)
@@ -1216,6 +1346,7 @@ template struct KuuInvLauncher<ASVGP_ELBO_ONLY_K>;
 #endif
 #if !defined(ASVGP_ELBO_PART) || ASVGP_ELBO_PART == 2
 template struct PostLauncher<ASVGP_ELBO_ONLY_K>;
+template struct PostCovLauncher<ASVGP_ELBO_ONLY_K>;
 #endif
 #endif  // ASVGP_ELBO_ONLY_K
 
@@ -1377,6 +1508,32 @@ extern "C" int asvgp_posterior_prepare_1d(asvgp_handle_t handle, const double* s
 #define POST_CASE(KK) case KK: return PostLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st);
   switch (k) { POST_CASE(1) POST_CASE(2) POST_CASE(3) POST_CASE(4) POST_CASE(5) POST_CASE(6) }
 #undef POST_CASE
+  return ASVGP_ERR_UNSUPPORTED;
+}
+
+extern "C" size_t asvgp_posterior_cov_workspace_bytes(int64_t M, int k, int64_t D) {
+  if (M < 1 || k < 1 || k > ASVGP_MAX_ORDER || D < 1) return 0;
+  return sizeof(double) * (ws_doubles(M, k, D) + cov_ws_doubles(M, k));
+}
+
+extern "C" int asvgp_posterior_cov_prepare_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
+                                              double lengthscale, double noise_variance, int64_t M, int k, int64_t D,
+                                              double* alpha, double* W, double* W_dense, int* info, void* workspace, size_t workspace_bytes,
+                                              asvgp_stream_t stream) {
+  int rc = elbo_args_ok(stats, static_bands, alpha, M, k, D, variance, lengthscale, noise_variance, workspace,
+                        workspace_bytes, info, "posterior_cov_prepare_1d");
+  if (rc) return rc;
+  if (!W || !W_dense) { set_error("posterior_cov_prepare_1d: bad argument"); return ASVGP_ERR_BAD_ARG; }
+  if (workspace_bytes < asvgp_posterior_cov_workspace_bytes(M, k, D)) {
+    set_error("posterior_cov_prepare_1d: workspace too small (asvgp_posterior_cov_workspace_bytes)");
+    return ASVGP_ERR_WORKSPACE;
+  }
+  Handle* h = as_handle(handle);
+  { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }
+  hipStream_t st = as_stream(stream);
+#define COV_CASE(KK) case KK: return PostCovLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, W_dense, info, workspace, st);
+  switch (k) { COV_CASE(1) COV_CASE(2) COV_CASE(3) COV_CASE(4) COV_CASE(5) COV_CASE(6) }
+#undef COV_CASE
   return ASVGP_ERR_UNSUPPORTED;
 }
 

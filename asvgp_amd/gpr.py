@@ -156,6 +156,8 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._out = torch.zeros(8, dtype=torch.float64, device=dev)
         self._info = torch.zeros(2, dtype=torch.int32, device=dev)
         self._post = None
+        self._post_cov = None                 # (theta, W_dense): the dense P^-1 - Kuu^-1 of predict_f_cov_device
+        self._cov_ws = None
         self._host_result = np.zeros(10)      # [out[0..7], info[0], info[1]] of the last host-read evaluation
         self._mirror_read = lib.asvgp_result_mirror_read
         self._publish = lib.asvgp_elbo_publish_theta
@@ -406,6 +408,89 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
                                            alpha.data_ptr(), W.data_ptr(), float(self.kernel.variance), self.D,
                                            mean.data_ptr(), var.data_ptr(), stream_ptr()), "predict_1d")
         return mean, var
+
+    # -- full posterior covariance (not in the reference: its predict_f(full_cov=True) raises, gpr.py:113) ------------
+    def _posterior_cov(self):
+        """asvgp_posterior_cov_prepare_1d once per theta: W_dense = P^-1 - Kuu^-1 (M x M, device), cached beside _post."""
+        v, l, s = self.theta()
+        key = (v, l, s)
+        if self._post_cov is not None and self._post_cov[0] == key:
+            return self._post_cov[1]
+        self._post_cov = None
+        b = self.basis
+        k, M, D = self.bandwidth, b.m, self.D
+        lib = get_lib()
+        dev = self._stats.device
+        if self._cov_ws is None:   # zero-filled once (the chain's arrival slots), like _elbo_ws
+            self._cov_ws = torch.zeros(lib.asvgp_posterior_cov_workspace_bytes(M, k, D) // 8, dtype=torch.float64, device=dev)
+        alpha = torch.empty((M, D), dtype=torch.float64, device=dev)
+        W = torch.empty((k + 1, M), dtype=torch.float64, device=dev)
+        Wd = torch.empty((M, M), dtype=torch.float64, device=dev)
+        S = self._statics()
+        check(lib.asvgp_posterior_cov_prepare_1d(self._h.ptr, self._stats.data_ptr(), S.data_ptr(), self.kernel.kind, v, l, s, M, k, D,
+                                                 alpha.data_ptr(), W.data_ptr(), Wd.data_ptr(), self._info.data_ptr(),
+                                                 self._cov_ws.data_ptr(), self._cov_ws.numel() * 8, stream_ptr()),
+              "posterior_cov_prepare_1d")
+        try:
+            self._check_pd()
+        except AsvgpError:
+            self._cov_ws.zero_()
+            raise
+        self._post_cov = (key, Wd)
+        return Wd
+
+    def predict_f_cov_device(self, X1, X2=None):
+        """Posterior cross-covariance cov[f(X1), f(X2)] (n1, n2) as a device tensor; X2=None means X1 against itself.
+        k(x, x') + phi(x)^T (P^-1 - Kuu^-1) phi(x') in one kernel (asvgp_predict_cov_1d); its diagonal is predict_f's variance."""
+        Wd = self._posterior_cov()
+        b = self.basis
+        x1 = _to_device(X1, self._stats.device).reshape(-1)
+        x2 = x1 if X2 is None else _to_device(X2, self._stats.device).reshape(-1)
+        n1, n2 = x1.shape[0], x2.shape[0]
+        cov = torch.empty((n1, n2), dtype=torch.float64, device=x1.device)
+        check(get_lib().asvgp_predict_cov_1d(self._h.ptr, x1.data_ptr(), n1, x2.data_ptr(), n2, b.mesh.data_ptr(), b.mesh.shape[0],
+                                             b.delta_np, b.order, b.m, Wd.data_ptr(), self.kernel.kind, float(self.kernel.variance),
+                                             float(self.kernel.lengthscales), cov.data_ptr(), n2, stream_ptr()), "predict_cov_1d")
+        return cov
+
+    def predict_f_full_cov(self, Xnew):
+        """numpy (mean (n, D), cov (D, n, n)): gpflow's predict_f(full_cov=True) layout.  All D outputs share one covariance, so cov
+        is a read-only broadcast of one n x n matrix."""
+        mean, _ = self.predict_f_device(Xnew)
+        cov = self.predict_f_cov_device(Xnew).cpu().numpy()
+        return mean.cpu().numpy(), np.broadcast_to(cov, (self.D,) + cov.shape)
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, jitter=1e-6, seed=None):
+        """Posterior function samples, numpy (num_samples, n, D), or (n, D) when num_samples is None (gpflow's layout).
+        full_cov=True: mean + L z with L = cholesky(cov + jitter I) on the device; full_cov=False: independent draws from the
+        marginals of predict_f_device.  seed seeds a device torch.Generator: the same seed gives the same samples."""
+        mean, var = self.predict_f_device(Xnew)
+        n, D = mean.shape
+        S = 1 if num_samples is None else int(num_samples)
+        gen = torch.Generator(device=mean.device)
+        if seed is None:
+            gen.seed()
+        else:
+            gen.manual_seed(int(seed))
+        z = torch.randn((S, n, D), generator=gen, dtype=torch.float64, device=mean.device)
+        if full_cov:
+            cov = self.predict_f_cov_device(Xnew)
+            cov.diagonal().add_(float(jitter))
+            L, info = torch.linalg.cholesky_ex(cov)
+            if int(info.item()) != 0 or not bool(torch.isfinite(L).all()):
+                raise NotPositiveDefiniteError("posterior covariance + jitter * I is not positive definite (jitter = %g%s)"
+                                               % (jitter, ", column %d" % (int(info.item()) - 1) if int(info.item()) > 0 else ""))
+            f = mean + torch.matmul(L, z)
+        else:
+            f = mean + var.clamp_min(0.0).sqrt() * z
+        f = f.cpu().numpy()
+        return f[0] if num_samples is None else f
+
+    def close(self):
+        """Also releases the cached dense W and its workspace."""
+        self._post_cov = None
+        self._cov_ws = None
+        super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False, batch=False):
         """gpr.py:91-136.  Returns numpy (mean, var) like the reference.  batch=True reproduces the reference's

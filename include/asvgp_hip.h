@@ -323,6 +323,27 @@ int asvgp_predict_1d_h(asvgp_handle_t handle, const double* xnew, int64_t n, con
                        double* var, asvgp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Posterior covariance   what GPR_1d.predict_f(full_cov=True) would return (the reference raises, gpr.py:113)
+ * cov[f(x), f(x')] = k(x, x') + phi(x)^T W_dense phi(x'),  W_dense = P^-1 - Kuu^-1  (M x M, symmetric); its diagonal is the
+ * variance of asvgp_predict_1d.
+ * cov_prepare: the posterior_prepare chain (same alpha, same band W) and W_dense, row-major, both triangles, once per theta.
+ * The band entries of W_dense are W bit for bit; the others come from back substitution with L^T along each row,
+ * S[i, j] = -(1 / L[j, j]) sum_{l=1..k} L[j+l, j] S[i, j+l] (i > j), seeded by the row's band entries, for Kuu and for P (L from
+ * asvgp_cholesky_band).  workspace: asvgp_posterior_cov_workspace_bytes(M, k, D), zero-filled once by the caller; its head is an
+ * ELBO workspace (asvgp_elbo_workspace_bytes) of its own.  info as asvgp_posterior_prepare_1d's.
+ * predict_cov: cov[a * ldc + b] = k(x1_a, x2_b) + phi(x1_a)^T W_dense phi(x2_b) for a < n1, b < n2 (the gpflow Matern of `kind`).
+ * ASVGP_ERR_UNSUPPORTED when order > 6 or a row of W_dense (8 M bytes) exceeds 156 KiB of LDS.  The handle may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+size_t asvgp_posterior_cov_workspace_bytes(int64_t M, int k, int64_t D);
+int asvgp_posterior_cov_prepare_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
+                                   double lengthscale, double noise_variance, int64_t M, int k, int64_t D,
+                                   double* alpha, double* W, double* W_dense, int* info, void* workspace, size_t workspace_bytes,
+                                   asvgp_stream_t stream);
+int asvgp_predict_cov_1d(asvgp_handle_t handle, const double* x1, int64_t n1, const double* x2, int64_t n2, const double* mesh,
+                         int64_t n_mesh, double delta, int order, int64_t M, const double* W_dense, int kind, double variance,
+                         double lengthscale, double* cov, int64_t ldc, asvgp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 2-D Kronecker (tensor-product) path   replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
  * linear algebra of GPR_kron gpr.py:239-359 (KufKfu.todense(), tf.linalg.cholesky / triangular_solve / cholesky_solve).
  * Basis pair (i1, i2) has row index i1*m2 + i2 (dim-0 major, as make_kvs_two_sparse).  Both bases share `order` = k
