@@ -74,6 +74,8 @@ SIGNATURES = {
     "asvgp_posterior_cov_workspace_bytes": (_Z, [_L, _I, _L]),
     "asvgp_posterior_cov_prepare_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _I, _L, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_predict_cov_1d": (_I, [_P, _P, _L, _P, _L, _P, _L, _D, _I, _L, _P, _I, _D, _D, _P, _L, _P]),
+    "asvgp_kron_dense_inverse": (_I, [_P, _P, _P, _L, _L, _I, _L, _L, _L, _L, _P, _P]),
+    "asvgp_predict_cov_kron2d": (_I, [_P, _P, _L, _P, _L, _P, _L, _D, _L, _P, _L, _D, _L, _I, _P, _P, _P, _I, _D, _D, _I, _D, _D, _P, _L, _P]),
     "asvgp_profile_enable": (_I, [_P, _I]),
     "asvgp_profile_read": (_I, [_P, _c.POINTER(_D), _c.POINTER(_L)]),
     "asvgp_kron_stats_doubles": (_Z, [_L, _L, _I]),

@@ -559,6 +559,7 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         self.tr_yTy = self._stats[-1]
         self._info = torch.zeros(1, dtype=torch.int32, device=dev)
         self._post = None
+        self._post_cov = None                 # (key, Sigma, [K1^-1, K2^-1], the _post it was completed from) of predict_f_cov_device
 
     # ---- d != 2: dense tensor-product route, as the reference does it for every d (kronecker.py:32-33 folds over any d;
     # gpr.py:266-272 densifies Kuf Kuf^T, 286-308 dense Cholesky).  The statistics are [M_tot^2 dense Kuf Kuf^T | Kuf y | y^T y]
@@ -588,6 +589,7 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         self.tr_yTy = self._stats[-1]
         self._info = torch.zeros(1, dtype=torch.int32, device=dev)
         self._post = None
+        self._post_cov = None                 # (key, Sigma, [K1^-1, K2^-1], the _post it was completed from) of predict_f_cov_device
 
     def _dense_rows(self, X):
         """Khatri-Rao design matrix (M_tot, n) of a chunk of points, dim-0 major (kronecker.py:27-33)."""
@@ -1088,9 +1090,13 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         SigD[nblk - 1] = Dinv[nblk - 1]
         if nblk > 1:
             G = sub @ Linv[:-1]                                   # G_i = L_{i+1,i} L_ii^-1
+            if f.get("keep_G"):
+                f["G"] = G                                        # (for the dense Sigma of _posterior_cov, which drops it again)
             for i in range(nblk - 2, -1, -1):
                 SigS[i] = -(SigD[i + 1] @ G[i])
                 SigD[i] = Dinv[i] - G[i].t() @ SigS[i]
+        if f.get("keep_G"):
+            f.setdefault("G", None)                               # (one block: no G)
         if f.get("alpha") is None:   # alpha = L^-T c on the same blocks (40 small matrix-vector steps instead of 512 band launches)
             cb = torch.zeros(nblk * Bb, dtype=torch.float64, device=dev)
             cb[:M] = f["c"].reshape(-1)
@@ -1117,6 +1123,8 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         LinvT = Linv.transpose(-1, -2)
         Dinv = (LinvT @ Linv).transpose(0, 1).contiguous()       # step-major [nb-1][2][Bb][Bb]: a step's operands are one contiguous batch
         Gs = (sub @ Linv).transpose(0, 1).contiguous()            # G_i = L_{i+1,i} L_ii^-1
+        if f.get("keep_G"):
+            f["G"] = Gs                                           # (for the dense Sigma of _posterior_cov, which drops it again)
         GsT = Gs.transpose(-1, -2)
         yb = torch.stack((f["y_top"], f["y_bot"])).view(2, nb, Bb) / s
         Wv = (LinvT @ yb[:, :nb - 1].unsqueeze(-1)).transpose(0, 1).contiguous()        # L_i^-T y_i, [nb-1][2][Bb][1]
@@ -1215,6 +1223,87 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
             p.unconstrained = float(ui)
         self._post = None
         return res
+
+    # -- full posterior covariance (d = 2; not in the reference: its predict_f(full_cov=True) raises, gpr.py:310-334) ---------
+    def _require_2d(self, what):
+        if self._dense_mode:
+            raise NotImplementedError("GPR_kron.%s exists for d = 2 only (this model has d = %d)" % (what, self.d))
+
+    def _posterior_cov(self):
+        """(Sigma, [K1^-1, K2^-1]) once per theta and layout: Sigma = P^-1 dense (M_tot x M_tot) from the selected inverse of _post
+        (asvgp_kron_dense_inverse), K_d^-1 dense per dimension (torch cholesky_inverse of the m_d x m_d Kuu band: negligible next to Sigma)."""
+        v, s = self.theta()
+        lay = self._twist_layout()
+        key = (tuple(v), s, None if lay is None else tuple(sorted(lay.items())))
+        if self._post_cov is not None and self._post_cov[0] == key and self._post_cov[3] is self._post:
+            return self._post_cov[1], self._post_cov[2]
+        self._post_cov = None
+        th = self.theta()
+        if self._post is None or self._post[0] != th or self._post[1].get("twist") != lay or "G" not in self._post[1]:
+            f = self._factor(want_alpha=False)
+            f["keep_G"] = True                                    # (_selinv keeps G_i = L_{i+1,i} L_ii^-1 until Sigma is built)
+            self._post = (th, f, self._selinv(f))                # (also fills f["alpha"])
+        f, (SigD, SigS, Bb) = self._post[1], self._post[2]
+        lib = get_lib()
+        M = self.Mtot
+        dev = self._stats.device
+        Sig = torch.empty((M, M), dtype=torch.float64, device=dev)
+        if lay is None:
+            nb = (M + Bb - 1) // Bb
+            G = f.pop("G", None)
+            check(lib.asvgp_kron_dense_inverse(G.data_ptr() if nb > 1 else None, SigD.data_ptr(), SigS.data_ptr() if nb > 1 else None, M, Bb,
+                                               0, nb, 0, 0, 0, Sig.data_ptr(), stream_ptr()), "kron_dense_inverse")
+        else:
+            G = f.pop("G").transpose(0, 1).contiguous()          # step-major [nb-1][2] -> stack-major [2][nb-1], SigS's layout
+            check(lib.asvgp_kron_dense_inverse(G.data_ptr(), SigD.data_ptr(), SigS.data_ptr(), M, Bb, 1, lay["nb"], lay["top_end"], lay["padt"],
+                                               lay["padb"], Sig.data_ptr(), stream_ptr()), "kron_dense_inverse")
+            del G
+        Kinv = []
+        for i, K in enumerate(f["Ks"]):
+            L, info = torch.linalg.cholesky_ex(utils.band_to_dense_sym(K))
+            if int(info.item()):
+                raise NotPositiveDefiniteError("Kuu of dimension %d not positive definite at column %d" % (i, int(info.item()) - 1))
+            Kinv.append(torch.cholesky_inverse(L).contiguous())
+        self._post_cov = (key, Sig, Kinv, self._post)          # (reused while theta, the layout and the posterior it came from stand)
+        return Sig, Kinv
+
+    def predict_f_cov_device(self, X1, X2=None):
+        """Posterior cross-covariance cov[f(X1), f(X2)] (n1, n2) as a device tensor; X2=None means X1 against itself.  X: (n, 2).
+        k1 k2 + phi^T P^-1 phi' - (phi1^T K1^-1 phi1')(phi2^T K2^-1 phi2') in one kernel (asvgp_predict_cov_kron2d); its diagonal is
+        predict_f's variance."""
+        self._require_2d("predict_f_cov_device")
+        Sig, (K1i, K2i) = self._posterior_cov()
+        b1, b2 = self.bases
+        k1, k2 = self.kernels
+        dev = self._stats.device
+        x1 = _to_device(X1, dev).reshape(-1, 2).contiguous()
+        x2 = x1 if X2 is None else _to_device(X2, dev).reshape(-1, 2).contiguous()
+        n1, n2 = x1.shape[0], x2.shape[0]
+        cov = torch.empty((n1, n2), dtype=torch.float64, device=dev)
+        check(get_lib().asvgp_predict_cov_kron2d(None, x1.data_ptr(), n1, x2.data_ptr(), n2, b1.mesh.data_ptr(), b1.mesh.shape[0], b1.delta_np,
+                                                 b1.m, b2.mesh.data_ptr(), b2.mesh.shape[0], b2.delta_np, b2.m, self.order, Sig.data_ptr(),
+                                                 K1i.data_ptr(), K2i.data_ptr(), k1.kind, float(k1.variance), float(k1.lengthscales), k2.kind,
+                                                 float(k2.variance), float(k2.lengthscales), cov.data_ptr(), n2, stream_ptr()),
+              "predict_cov_kron2d")
+        return cov
+
+    def predict_f_full_cov(self, Xnew):
+        """numpy (mean (n, 1), cov (1, n, n)): gpflow's predict_f(full_cov=True) layout, cov a read-only broadcast."""
+        self._require_2d("predict_f_full_cov")
+        mean, _ = self.predict_f_device(Xnew)
+        cov = self.predict_f_cov_device(Xnew).cpu().numpy()
+        return mean.cpu().numpy(), np.broadcast_to(cov, (1,) + cov.shape)
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, jitter=1e-6, seed=None):
+        """Posterior function samples, numpy (num_samples, n, 1), or (n, 1) when num_samples is None: GPR_1d.predict_f_samples on
+        this model's predict_f_device / predict_f_cov_device (same seed and jitter semantics, NotPositiveDefiniteError alike)."""
+        self._require_2d("predict_f_samples")
+        return GPR_1d.predict_f_samples(self, Xnew, num_samples, full_cov, jitter, seed)
+
+    def close(self):
+        """Also releases the cached dense Sigma and K_d^-1."""
+        self._post_cov = None
+        super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """gpr.py:310-334: (mean, var) as numpy (n,1); var = prod v + |L_P^-1 phi*|^2 - phi*^T Kuu^-1 phi*."""

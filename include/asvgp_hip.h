@@ -443,6 +443,24 @@ int asvgp_predict_kron2d_var_twisted(const double* Xnew, int64_t n, const double
                                      const double* SigD, const double* SigS, int64_t Bb, int64_t nb, int64_t top_end, int64_t padt,
                                      int64_t padb, double* qp, asvgp_stream_t stream);
 
+/* Full posterior covariance of the 2-D model (GPR_kron.predict_f_cov_device; the reference's predict_f(full_cov=True) raises):
+ *   cov[f(x), f(x')] = k1(x_1, x'_1) k2(x_2, x'_2) + phi(x)^T Sigma phi(x') - (phi1^T K1^-1 phi1')(phi2^T K2^-1 phi2'),  Sigma = P^-1.
+ * kron_dense_inverse: the whole of Sigma (M_tot x M_tot, row-major, both triangles, original ordering; caller-owned) from the selected
+ * inverse on the band and G_j = L_{j+1,j} L_jj^-1: for every block row i eliminated after block column j, Sigma_{i,j} = -Sigma_{i,j+1} G_j,
+ * one launch per j (fp64 MFMA products).  The blocks SigD / SigS hold are copied in unchanged (SigS mirrored), so the band equals them
+ * bit for bit.  twisted = 0: one-sided layout, nb = ceil(M / Bb), top_end = padt = padb = 0, G / SigS [nb-1][Bb][Bb], SigD [nb][Bb][Bb];
+ * twisted = 1: the layout of asvgp_kron_assemble_twisted (its consistency rule; padb may equal Bb, block 0 of the bottom stack then being all padding), G / SigS [2][nb-1][Bb][Bb], SigD [2][nb][Bb][Bb] (stack 0 = top,
+ * stack 1 = bottom, reversed).  Bb: a multiple of 32.  G / SigS may be NULL when nb = 1.
+ * predict_cov_kron2d: cov[a * ldc + b] for a < n1, b < n2; x1, x2 (n, 2) row-major; Sigma from kron_dense_inverse; K1inv, K2inv the
+ * dense m_d x m_d inverses of the 1-D Kuu; kind / variance / lengthscale per dimension (gpflow's Matern).  ASVGP_ERR_UNSUPPORTED when
+ * order > 6 or (M_tot + m1 + m2) doubles exceed 156 KiB of LDS.  The handle may be NULL. */
+int asvgp_kron_dense_inverse(const double* G, const double* SigD, const double* SigS, int64_t M, int64_t Bb, int twisted, int64_t nb,
+                             int64_t top_end, int64_t padt, int64_t padb, double* Sigma, asvgp_stream_t stream);
+int asvgp_predict_cov_kron2d(asvgp_handle_t handle, const double* x1, int64_t n1, const double* x2, int64_t n2, const double* mesh1,
+                             int64_t n_mesh1, double delta1, int64_t m1, const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2,
+                             int order, const double* Sigma, const double* K1inv, const double* K2inv, int kind1, double variance1,
+                             double lengthscale1, int kind2, double variance2, double lengthscale2, double* cov, int64_t ldc,
+                             asvgp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Additive model (GPR_additive, gpr.py:139-236): Kuf = vstack(Kuf_1 .. Kuf_d), so Kuf Kuf^T (gpr.py:170-171) has the
