@@ -1413,6 +1413,7 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
         self.tr_yTy = self._stats[self._diag_off[0] + (k + 2) * ms[0]]      # gpr.py:168
         self._info = torch.zeros(1, dtype=torch.int32, device=dev)
         self._dense = None
+        self._post_cov = None                 # (key, W, concatenated meshes) of predict_f_cov_device
 
     # ------------------------------------------------------------------------------------------------------
     def _phi_pass_local(self):
@@ -1432,6 +1433,7 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
                                          bj.delta_np, bj.m, k, self._stats[o:].data_ptr(), self._ws.data_ptr(), self._wsb,
                                          stream_ptr()), "phi_cross_2d")
         self._dense = None
+        self._post_cov = None                 # (W was built from the statistics just replaced)
         return self._stats
 
     def _band(self, i):
@@ -1619,6 +1621,77 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
         mean = torch.cat(means, 0) if means else torch.zeros((0, 1), dtype=torch.float64, device=Xn.device)
         var = torch.cat(vars_, 0) if vars_ else torch.zeros(0, dtype=torch.float64, device=Xn.device)
         return mean, var.reshape(-1, 1).repeat(1, self.y.shape[1])                  # gpr.py:233-234
+
+    # -- full posterior covariance (not in the reference: its predict_f ignores full_cov, gpr.py:211-236) ---------------------
+    def _posterior_cov(self):
+        """W = P^-1 - blockdiag(K_1^-1 .. K_d^-1) (M_tot x M_tot, device) once per theta: cholesky_inverse of the dense factor of
+        _factor, then each dimension's dense K_i^-1 (torch cholesky_inverse of the m_i x m_i Kuu band) subtracted from its block.
+        Cached on _post_cov with the concatenated meshes; _phi_pass_local and close() drop it."""
+        v, s = self.theta()
+        key = (tuple(v), s)
+        if self._post_cov is not None and self._post_cov[0] == key:
+            return self._post_cov[1], self._post_cov[2]
+        self._post_cov = None
+        f = self._factor()
+        W = self._minus_kuu_inverse(torch.cholesky_inverse(f["L"]), f["Ks"])
+        meshes = torch.cat([bs.mesh.reshape(-1) for bs in self.bases]).contiguous()
+        self._post_cov = (key, W, meshes)
+        return W, meshes
+
+    def _minus_kuu_inverse(self, W, Ks):
+        """W - blockdiag(K_1^-1 .. K_d^-1), symmetrised; W is overwritten.  Dimensions of equal m_i share one batched factorisation
+        and inverse."""
+        groups = {}
+        for i, bs in enumerate(self.bases):
+            groups.setdefault(bs.m, []).append(i)
+        for dims in groups.values():
+            L, info = torch.linalg.cholesky_ex(torch.stack([utils.band_to_dense_sym(Ks[i]) for i in dims]))
+            for i, col in zip(dims, info.tolist()):
+                if col:
+                    raise NotPositiveDefiniteError("Kuu of dimension %d not positive definite at column %d" % (i, col - 1))
+            Kinv = torch.cholesky_inverse(L)
+            for j, i in enumerate(dims):
+                a, b = self.offsets[i], self.offsets[i + 1]
+                W[a:b, a:b] -= Kinv[j]
+        return (0.5 * (W + W.t())).contiguous()   # (exactly symmetric: cov(X1, X2) = cov(X2, X1)^T up to the rounding of the sums)
+
+    def predict_f_cov_device(self, X1, X2=None):
+        """Posterior cross-covariance cov[f(X1), f(X2)] (n1, n2) as a device tensor; X2=None means X1 against itself.  X: (n, d).
+        sum_i k_i(x_i, x'_i) + phi(x)^T W phi(x') in one kernel (asvgp_predict_cov_additive); its diagonal is predict_f's variance."""
+        dev, d = self._stats.device, self.d
+        x1 = _to_device(X1, dev).reshape(-1, d).contiguous()
+        x2 = x1 if X2 is None else _to_device(X2, dev).reshape(-1, d).contiguous()
+        n1, n2 = x1.shape[0], x2.shape[0]
+        cov = torch.empty((n1, n2), dtype=torch.float64, device=dev)
+        if n1 == 0 or n2 == 0:
+            return cov
+        W, meshes = self._posterior_cov()
+        arr = lambda t, vals: (t * d)(*vals)
+        check(get_lib().asvgp_predict_cov_additive(None, x1.data_ptr(), n1, x2.data_ptr(), n2, d, meshes.data_ptr(),
+                                                   arr(ctypes.c_int64, [bs.mesh.shape[0] for bs in self.bases]),
+                                                   arr(ctypes.c_double, [bs.delta_np for bs in self.bases]),
+                                                   arr(ctypes.c_int64, [bs.m for bs in self.bases]), self.bandwidth,
+                                                   arr(ctypes.c_int, [kn.kind for kn in self.kernels]),
+                                                   arr(ctypes.c_double, [float(kn.variance) for kn in self.kernels]),
+                                                   arr(ctypes.c_double, [float(kn.lengthscales) for kn in self.kernels]),
+                                                   W.data_ptr(), cov.data_ptr(), n2, stream_ptr()), "predict_cov_additive")
+        return cov
+
+    def predict_f_full_cov(self, Xnew):
+        """numpy (mean (n, 1), cov (1, n, n)): gpflow's predict_f(full_cov=True) layout, cov a read-only broadcast."""
+        mean, _ = self.predict_f_device(Xnew)
+        cov = self.predict_f_cov_device(Xnew).cpu().numpy()
+        return mean.cpu().numpy(), np.broadcast_to(cov, (1,) + cov.shape)
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, jitter=1e-6, seed=None):
+        """Posterior function samples, numpy (num_samples, n, 1), or (n, 1) when num_samples is None: GPR_1d.predict_f_samples on
+        this model's predict_f_device / predict_f_cov_device (same seed and jitter semantics, NotPositiveDefiniteError alike)."""
+        return GPR_1d.predict_f_samples(self, Xnew, num_samples, full_cov, jitter, seed)
+
+    def close(self):
+        """Also releases the cached dense W."""
+        self._post_cov = None
+        super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         mean, var = self.predict_f_device(Xnew)

@@ -474,6 +474,19 @@ int asvgp_phi_cross_2d(const double* x_i, const double* x_j, int64_t N, const do
                        double delta_i, int64_t m_i, const double* mesh_j, int64_t n_mesh_j, double delta_j, int64_t m_j,
                        int order, double* out, void* workspace, size_t workspace_bytes, asvgp_stream_t stream);
 
+/* Full posterior covariance of the additive model (GPR_additive.predict_f_cov_device; the reference's predict_f ignores full_cov):
+ *   cov[a * ldc + b] = sum_i k_i(x1[a, i], x2[b, i]) + phi(x1_a)^T W phi(x2_b),   a < n1, b < n2,
+ *   W = P^-1 - blockdiag(K_1^-1 .. K_d^-1)  (M_tot x M_tot, row-major; block i at rows / columns off_i = m_0 + .. + m_{i-1}).
+ * x1, x2: (n, d) row-major.  meshes: the d meshes concatenated on the device (n_mesh[0] knots of dimension 0, then dimension 1, ..).
+ * n_mesh, delta, m, kind, variance, lengthscale: HOST arrays of d entries (gpflow's Matern per dimension); one shared order.  The
+ * per-dimension scalars are copied into the kernel's arguments, so the call is stream-ordered and capturable.  ASVGP_ERR_UNSUPPORTED
+ * when order > 6, d > ASVGP_ADDITIVE_COV_MAX_D or M_tot doubles exceed 156 KiB of LDS.  The handle may be NULL. */
+enum { ASVGP_ADDITIVE_COV_MAX_D = 16 };
+int asvgp_predict_cov_additive(asvgp_handle_t handle, const double* x1, int64_t n1, const double* x2, int64_t n2, int d,
+                               const double* meshes, const int64_t* n_mesh, const double* delta, const int64_t* m, int order,
+                               const int* kind, const double* variance, const double* lengthscale, const double* W, double* cov,
+                               int64_t ldc, asvgp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, HIP events are recorded on the launch stream immediately around
  * every Phi-pass kernel launch (up to 1024 launches); asvgp_profile_read synchronises on them and returns the
