@@ -74,6 +74,10 @@ SIGNATURES = {
     "asvgp_posterior_cov_workspace_bytes": (_Z, [_L, _I, _L]),
     "asvgp_posterior_cov_prepare_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _I, _L, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_predict_cov_1d": (_I, [_P, _P, _L, _P, _L, _P, _L, _D, _I, _L, _P, _I, _D, _D, _P, _L, _P]),
+    "asvgp_predict_deriv_1d": (_I, [_P, _P, _L, _P, _L, _D, _I, _L, _P, _P, _I, _D, _D, _L, _P, _P, _P]),
+    "asvgp_predict_cov_deriv_1d": (_I, [_P, _P, _L, _P, _L, _P, _L, _D, _I, _L, _P, _I, _D, _D, _I, _I, _P, _L, _P]),
+    "asvgp_predict_grad_kron2d": (_I, [_P, _L, _P, _L, _D, _L, _P, _L, _D, _L, _I, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L,
+                                       _I, _D, _D, _I, _D, _D, _P, _P, _P]),
     "asvgp_kron_dense_inverse": (_I, [_P, _P, _P, _L, _L, _I, _L, _L, _L, _L, _P, _P]),
     "asvgp_predict_cov_kron2d": (_I, [_P, _P, _L, _P, _L, _P, _L, _D, _L, _P, _L, _D, _L, _I, _P, _P, _P, _I, _D, _D, _I, _D, _D, _P, _L, _P]),
     "asvgp_predict_cov_additive": (_I, [_P, _P, _L, _P, _L, _I, _P, _c.POINTER(_L), _c.POINTER(_D), _c.POINTER(_L), _I,

@@ -1394,6 +1394,110 @@ __global__ void predict_kron2d_var_kernel(const double* __restrict__ X, long n, 
   qp[p] = q;
 }
 
+// Posterior gradient of the 2-D model per test point (asvgp_predict_grad_kron2d).  psi_1 = phi1' (x) phi2, psi_2 = phi1 (x) phi2':
+//   mean2[2p + i] = psi_i^T alpha,
+//   cov3[3p + (0, 1, 2)] = (C_11, C_12, C_22),  C_ij = [i = j] prior_i + psi_i^T Sigma psi_j - (phi1^(a)T S1 phi1^(b))(phi2^(c)T S2 phi2^(d)),
+// (a, b, c, d) = (1, 1, 0, 0), (1, 0, 0, 1), (0, 0, 1, 1).  Every index pair lies in the point's (k+1)^2 window, inside the band: each
+// Sigma entry of the window's lower triangle is read once through SigView and feeds all three quadratic forms.  Row ra of basis pair
+// (a, b) is (i1 + K - a) m2 + i2 + K - b, so rb <= ra exactly when a2 > a, or a2 == a and b2 >= b (|b - b2| <= K < m2).  The pairs
+// (a, a2) run as a rolled loop (wave-uniform trip counts) around a fully unrolled (k+1)^2 block over (b, b2): unrolling all
+// (k+1)^4 / 2 reads let the compiler hoist the Sigma loads and spill (predict_kron2d_var_kernel's plan spills from k = 3 on).  Rolling
+// the b loop as well (k + 1 reads per step) took more registers, not fewer, and put v2 / d2 on the stack.
+template <int K>
+__device__ __forceinline__ double pick(const double (&v)[K + 1], int a) {   // v[a] for a wave-uniform a, without dynamic register indexing
+  double r = v[0];
+#pragma unroll
+  for (int i = 1; i <= K; ++i) r = (a == i) ? v[i] : r;
+  return r;
+}
+
+// the (b, b2) block of the pair (a, a2): DIAG (a2 == a) takes b2 >= b, the diagonal once and every other entry for both triangles.
+// The Sigma entries are read in place through SigView (no LDS staging: a point's window is its own).
+template <int K, bool DIAG>
+__device__ __forceinline__ void grad_window_block(const SigView& sig, long ra0, long rb0, double da, double va, double db, double vb,
+                                                  const double (&v2)[K + 1], const double (&d2)[K + 1], double& q11, double& q12,
+                                                  double& q22) {
+#pragma unroll
+  for (int b = 0; b <= K; ++b) {
+    const double pa1 = da * v2[b], pa2 = va * d2[b];               // psi_1, psi_2 at ra = ra0 - b
+#pragma unroll
+    for (int b2 = DIAG ? b : 0; b2 <= K; ++b2) {
+      const double sg = sig.at(ra0 - b, rb0 - b2);
+      const double pb1 = db * v2[b2], pb2 = vb * d2[b2];
+      if (DIAG && b2 == b) {
+        q11 = fma(pa1 * pb1, sg, q11);
+        q12 = fma(pa1 * pb2, sg, q12);
+        q22 = fma(pa2 * pb2, sg, q22);
+      } else {                                                     // (ra, rb) and (rb, ra)
+        q11 = fma(2.0 * pa1 * pb1, sg, q11);
+        q12 = fma(fma(pa1, pb2, pb1 * pa2), sg, q12);
+        q22 = fma(2.0 * pa2 * pb2, sg, q22);
+      }
+    }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(128) void predict_kron2d_grad_kernel(const double* __restrict__ X, long n, const double* __restrict__ mesh1, int n1,
+                                                                  double id1, const double* __restrict__ mesh2, int n2, double id2, int m2,
+                                                                  const double* __restrict__ alpha, const double* __restrict__ S1, int m1,
+                                                                  const double* __restrict__ S2, SigView sig, double prior1, double prior2,
+                                                                  double* __restrict__ mean2, double* __restrict__ cov3) {
+  long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const double2 xv = *reinterpret_cast<const double2*>(X + 2 * p);
+  const int i1 = neighbour_index(xv.x, mesh1, n1, mesh1[0], id1);
+  const int i2 = neighbour_index(xv.y, mesh2, n2, mesh2[0], id2);
+  const double t1 = (xv.x - mesh1[i1]) * id1, t2 = (xv.y - mesh2[i2]) * id2;
+  double v1[K + 1], d1[K + 1], v2[K + 1], d2[K + 1];
+  bspline_pieces<K>(t1, v1);
+  bspline_pieces<K, 1>(t1, d1);
+  bspline_pieces<K>(t2, v2);
+  bspline_pieces<K, 1>(t2, d2);
+#pragma unroll
+  for (int i = 0; i <= K; ++i) { d1[i] *= id1; d2[i] *= id2; }
+  double mu1 = 0.0, mu2 = 0.0;
+#pragma unroll
+  for (int a = 0; a <= K; ++a)
+#pragma unroll
+    for (int b = 0; b <= K; ++b) {
+      const double al = alpha[(long)(i1 + K - a) * m2 + (i2 + K - b)];
+      mu1 = fma(d1[a] * v2[b], al, mu1);
+      mu2 = fma(v1[a] * d2[b], al, mu2);
+    }
+  double q11 = 0.0, q12 = 0.0, q22 = 0.0;
+#pragma unroll 1
+  for (int a = 0; a <= K; ++a) {
+    const double da = pick<K>(d1, a), va = pick<K>(v1, a);
+    const long ra0 = (long)(i1 + K - a) * m2 + (i2 + K);
+    grad_window_block<K, true>(sig, ra0, ra0, da, va, da, va, v2, d2, q11, q12, q22);
+#pragma unroll 1
+    for (int a2 = a + 1; a2 <= K; ++a2)
+      grad_window_block<K, false>(sig, ra0, (long)(i1 + K - a2) * m2 + (i2 + K), da, va, pick<K>(d1, a2), pick<K>(v1, a2), v2, d2, q11,
+                                  q12, q22);
+  }
+  // phi^(x)T S phi^(y) per dimension from the 1-D inverse bands S[d * m + lo]
+  double s1vv = 0.0, s1dv = 0.0, s1dd = 0.0, s2vv = 0.0, s2dv = 0.0, s2dd = 0.0;
+#pragma unroll
+  for (int a = 0; a <= K; ++a)
+#pragma unroll
+    for (int a2 = 0; a2 <= K; ++a2) {
+      const int lo = K - (a > a2 ? a : a2), d = a > a2 ? a - a2 : a2 - a;
+      const double e1 = S1[(long)d * m1 + i1 + lo], e2 = S2[(long)d * m2 + i2 + lo];
+      s1vv = fma(v1[a] * v1[a2], e1, s1vv);
+      s1dv = fma(d1[a] * v1[a2], e1, s1dv);
+      s1dd = fma(d1[a] * d1[a2], e1, s1dd);
+      s2vv = fma(v2[a] * v2[a2], e2, s2vv);
+      s2dv = fma(d2[a] * v2[a2], e2, s2dv);
+      s2dd = fma(d2[a] * d2[a2], e2, s2dd);
+    }
+  mean2[2 * p] = mu1;
+  mean2[2 * p + 1] = mu2;
+  cov3[3 * p] = prior1 + q11 - s1dd * s2vv;
+  cov3[3 * p + 1] = q12 - s1dv * s2dv;
+  cov3[3 * p + 2] = prior2 + q22 - s1vv * s2dd;
+}
+
 }  // namespace asvgp
 
 using namespace asvgp;
@@ -1667,6 +1771,56 @@ extern "C" int asvgp_predict_kron2d_var_twisted(const double* Xnew, int64_t n, c
   if (!twist_ok(m1 * m2, Bb, nb, top_end, padt, padb)) { set_error("predict_kron2d_var_twisted: inconsistent layout"); return ASVGP_ERR_BAD_ARG; }
   return predict_kron2d_var_entry(Xnew, n, mesh1, n_mesh1, delta1, mesh2, n_mesh2, delta2, m2, order,
                                   SigView{SigD, SigS, (int)Bb, (long)nb, (long)top_end, (long)padt, (long)(padb + m1 * m2 - 1)}, qp, stream);
+}
+
+// Posterior gradient of the 2-D model (GPR_kron.predict_f_gradient_device): mean (n, 2) and the three distinct entries of the (2, 2)
+// covariance per point, from alpha, the 1-D inverse bands and the selected inverse of P in either layout.
+extern "C" int asvgp_predict_grad_kron2d(const double* X, int64_t n, const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
+                                         const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order, const double* alpha,
+                                         const double* S1, const double* S2, const double* SigD, const double* SigS, int64_t Bb,
+                                         int twisted, int64_t nb, int64_t top_end, int64_t padt, int64_t padb, int kind1,
+                                         double variance1, double lengthscale1, int kind2, double variance2, double lengthscale2,
+                                         double* mean2, double* cov3, asvgp_stream_t stream) {
+  if (!X || !mesh1 || !mesh2 || !alpha || !S1 || !S2 || !SigD || !mean2 || !cov3 || n < 0 || m1 < 1 || m2 < 1 || !(delta1 > 0.0) ||
+      !(delta2 > 0.0) || !(variance1 > 0.0) || !(variance2 > 0.0) || !(lengthscale1 > 0.0) || !(lengthscale2 > 0.0) ||
+      (twisted != 0 && twisted != 1)) {
+    set_error("predict_grad_kron2d: bad argument");
+    return ASVGP_ERR_BAD_ARG;
+  }
+  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("predict_grad_kron2d: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
+  if (n_mesh1 != m1 - order + 1 || n_mesh2 != m2 - order + 1 || n_mesh1 < 2 || n_mesh2 < 2) {
+    set_error("predict_grad_kron2d: bad argument (n_mesh = %ld / %ld, m = %ld / %ld, order %d)", (long)n_mesh1, (long)n_mesh2, (long)m1,
+              (long)m2, order);
+    return ASVGP_ERR_BAD_ARG;
+  }
+  if (Bb < (int64_t)order * m2 + order) {
+    set_error("predict_grad_kron2d: bad argument (Bb = %ld below the bandwidth %ld)", (long)Bb, (long)(order * m2 + order));
+    return ASVGP_ERR_BAD_ARG;
+  }
+  const int64_t M = m1 * m2;
+  SigView sig{SigD, SigS, (int)Bb, 0, 0, 0, 0};
+  if (twisted) {
+    if (!twist_ok(M, Bb, nb, top_end, padt, padb)) { set_error("predict_grad_kron2d: inconsistent twisted layout"); return ASVGP_ERR_BAD_ARG; }
+    sig = SigView{SigD, SigS, (int)Bb, (long)nb, (long)top_end, (long)padt, (long)(padb + M - 1)};
+  }
+  if ((twisted || (M + Bb - 1) / Bb > 1) && !SigS) { set_error("predict_grad_kron2d: bad argument (SigS is null)"); return ASVGP_ERR_BAD_ARG; }
+  for (int kd : {kind1, kind2})
+    if (kd != ASVGP_MATERN32 && kd != ASVGP_MATERN52) {
+      set_error("predict_grad_kron2d: kernel kind %d has no mean-square derivative (only Matern-3/2 and Matern-5/2 do; Matern-1/2's "
+                "k''(0) is unbounded)", kd);
+      return ASVGP_ERR_UNSUPPORTED;
+    }
+  if (n == 0) return ASVGP_OK;
+  if ((reinterpret_cast<uintptr_t>(X) & 15) != 0) { set_error("predict_grad_kron2d: X must be 16-byte aligned (n,2) row-major"); return ASVGP_ERR_BAD_ARG; }
+  // prior gradient variance: -k_i''(0) k_other(0) = c_i v_i / l_i^2 * v_other (the cross term k1'(0) k2'(0) is zero)
+  const double c1 = kind1 == ASVGP_MATERN32 ? 3.0 : 5.0 / 3.0, c2 = kind2 == ASVGP_MATERN32 ? 3.0 : 5.0 / 3.0;
+  const double prior1 = c1 * variance1 / (lengthscale1 * lengthscale1) * variance2;
+  const double prior2 = c2 * variance2 / (lengthscale2 * lengthscale2) * variance1;
+  hipStream_t st = as_stream(stream);
+  KRON_DISPATCH(order, hipLaunchKernelGGL(predict_kron2d_grad_kernel<K>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, X, (long)n,
+                                          mesh1, (int)n_mesh1, 1.0 / delta1, mesh2, (int)n_mesh2, 1.0 / delta2, (int)m2, alpha, S1, (int)m1,
+                                          S2, sig, prior1, prior2, mean2, cov3));
+  return check_launch("predict_grad_kron2d");
 }
 
 extern "C" int asvgp_kron_cell_index(const double* X, int64_t N, const double* mesh1, int64_t n_mesh1, double delta1,

@@ -455,15 +455,20 @@ __global__ void phi_evaluate_kernel(const double* __restrict__ x, long N, const 
 // Posterior moments per test point: phi* has k+1 contiguous non-zeros, so
 // mean = sum_i phi_i alpha[row_i], var = v + sum_ij phi_i phi_j W[|r_i-r_j|][min(r_i,r_j)], W = band(P^-1)-band(Kuu^-1).
 // alpha, W and the mesh table are staged in LDS once per workgroup; 8 B in, 16 B out per point.
-// posterior of one test point from the staged tables: mean = phi*^T alpha, var = v + phi*^T W phi*  (W = band(P^-1) - band(Kuu^-1))
-template <int K>
+// posterior of one test point from the staged tables: mean = phi*^T alpha, var = v + phi*^T W phi*  (W = band(P^-1) - band(Kuu^-1)).
+// DERIV = 1: the same moments of f' (asvgp_predict_deriv_1d): phi' = (1/delta) bspline_pieces<K, 1>, `variance` the prior c v / l^2.
+template <int K, int DERIV = 0>
 __device__ __forceinline__ void predict_point(double xv, const double* mesh, int n_mesh, double m0, double inv_delta, int M,
                                               const double* alpha, const double* W, double variance, int D, long p,
                                               double* __restrict__ mean, double& var_out, double& mean0_out) {
   const int idx = neighbour_index(xv, mesh, n_mesh, m0, inv_delta);
   const double t = (xv - mesh[idx]) * inv_delta;
   double v[K + 1];
-  bspline_pieces<K>(t, v);
+  bspline_pieces<K, DERIV>(t, v);
+  if (DERIV) {
+#pragma unroll
+    for (int i = 0; i <= K; ++i) v[i] *= inv_delta;
+  }
   double q = 0.0;
 #pragma unroll
   for (int i = 0; i <= K; ++i) {      // row_i = idx + K - i
@@ -492,7 +497,7 @@ __device__ __forceinline__ void predict_point(double xv, const double* mesh, int
 // VEC4 (D == 1, 16-B aligned xnew / mean / var): two consecutive points per lane and iteration - one 16-B load, two
 // 16-B stores - with the next iteration's load issued before the LDS work.  The scalar form kept one 8-B load per lane in
 // flight (8 KB per CU): 0.6 TB/s of reads, 126 us for 10M points; latency-bound, not LDS-bound.
-template <int K, bool VEC4, bool STAGE>
+template <int K, bool VEC4, bool STAGE, int DERIV = 0>
 __global__ __launch_bounds__(1024) void predict_kernel(const double* __restrict__ xnew, long n,
                                                        const double* __restrict__ mesh_g, int n_mesh,
                                                        double inv_delta, int M, const double* __restrict__ alpha_g,
@@ -534,21 +539,21 @@ __global__ __launch_bounds__(1024) void predict_kernel(const double* __restrict_
       if (qn < nq) xa = x2[qn];   // next pair in flight under the LDS work
       double vo[2], mo[2];
 #pragma unroll
-      for (int u = 0; u < 2; ++u) predict_point<K>(xs[u], mesh, n_mesh, m0, inv_delta, M, alpha, W, variance, 1, 0, nullptr, vo[u], mo[u]);
+      for (int u = 0; u < 2; ++u) predict_point<K, DERIV>(xs[u], mesh, n_mesh, m0, inv_delta, M, alpha, W, variance, 1, 0, nullptr, vo[u], mo[u]);
       var2[q] = make_double2(vo[0], vo[1]);
       mean2[q] = make_double2(mo[0], mo[1]);
     }
     const long p = 2 * nq + (long)blockIdx.x * blockDim.x + threadIdx.x;   // the odd last point
     if (p < n) {
       double vo, mo;
-      predict_point<K>(xnew[p], mesh, n_mesh, m0, inv_delta, M, alpha, W, variance, 1, p, mean, vo, mo);
+      predict_point<K, DERIV>(xnew[p], mesh, n_mesh, m0, inv_delta, M, alpha, W, variance, 1, p, mean, vo, mo);
       var[p] = vo;
       mean[p] = mo;
     }
   } else {
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
       double vo, mo = 0.0;
-      predict_point<K>(xnew[p], mesh, n_mesh, m0, inv_delta, M, alpha, W, variance, D, p, mean, vo, mo);
+      predict_point<K, DERIV>(xnew[p], mesh, n_mesh, m0, inv_delta, M, alpha, W, variance, D, p, mean, vo, mo);
       var[p] = vo;
       if (D == 1) mean[p] = mo;
     }
@@ -1049,7 +1054,8 @@ extern "C" int asvgp_phi_evaluate_1d(const double* x, int64_t N, const double* m
   }
 }
 
-template <int K>
+// DERIV = 1: the moments of f' (asvgp_predict_deriv_1d) by the same plan; the cell-polynomial kernel serves DERIV = 0 only.
+template <int K, int DERIV = 0>
 static int launch_predict(Handle* h, const double* xnew, long n, const double* mesh, int n_mesh, double delta, int M,
                           const double* alpha, const double* W, double variance, int D, double* mean, double* var,
                           hipStream_t st) {
@@ -1059,7 +1065,7 @@ static int launch_predict(Handle* h, const double* xnew, long n, const double* m
   static const int poly_mode = getenv("ASVGP_PREDICT_POLY") ? atoi(getenv("ASVGP_PREDICT_POLY")) : 1;   // (0: the table-read kernel always - diagnostic)
   const size_t poly_bytes = predict_poly_lds_bytes<K>(n_mesh, M);
   double lin_step = 0.0;
-  if (h && poly_mode && D == 1 && n >= 262144 && poly_bytes <= 160 * 1024 - 64 && n_mesh >= 2 &&
+  if (DERIV == 0 && h && poly_mode && D == 1 && n >= 262144 && poly_bytes <= 160 * 1024 - 64 && n_mesh >= 2 &&
       handle_mesh_is_linspace(h, mesh, n_mesh, st, &lin_step, nullptr, nullptr)) {      // (verdict cached per mesh pointer; the kernel re-checks)
     auto pk = predict_poly_kernel<K>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)poly_bytes);
@@ -1077,15 +1083,15 @@ static int launch_predict(Handle* h, const double* xnew, long n, const double* m
   long blocks = ((vec4 ? (n + 1) / 2 : n) + threads - 1) / threads;
   long cap = stage ? 256 : 2048;
   if (blocks > cap) blocks = cap;
-  auto kern = stage ? (vec4 ? predict_kernel<K, true, true> : predict_kernel<K, false, true>)
-                    : (vec4 ? predict_kernel<K, true, false> : predict_kernel<K, false, false>);
+  auto kern = stage ? (vec4 ? predict_kernel<K, true, true, DERIV> : predict_kernel<K, false, true, DERIV>)
+                    : (vec4 ? predict_kernel<K, true, false, DERIV> : predict_kernel<K, false, false, DERIV>);
   if (stage) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), stage ? lds_bytes : 0, st, xnew, n, mesh,
                      n_mesh, 1.0 / delta, M, alpha, W, variance, D, stage, mean, var);
-  return check_launch("predict_1d");
+  return check_launch(DERIV ? "predict_deriv_1d" : "predict_1d");
 }
 
 static int predict_1d_entry(Handle* h, const double* xnew, int64_t n, const double* mesh, int64_t n_mesh, double delta,
@@ -1122,4 +1128,33 @@ extern "C" int asvgp_predict_1d_h(asvgp_handle_t handle, const double* xnew, int
   Handle* h = as_handle(handle);
   if (!h) { set_error("predict_1d_h: bad handle"); return ASVGP_ERR_BAD_ARG; }
   return predict_1d_entry(h, xnew, n, mesh, n_mesh, delta, order, M, alpha, W, variance, D, mean, var, stream);
+}
+
+// Moments of the derivative f' (GPR_1d.predict_f_gradient_device): mean = phi'^T alpha, var = c v / l^2 + phi'^T W phi', by
+// predict_kernel's plan (DERIV = 1).  c = 3 (Matern-3/2) or 5/3 (Matern-5/2); Matern-1/2 has no mean-square derivative.
+extern "C" int asvgp_predict_deriv_1d(asvgp_handle_t handle, const double* xnew, int64_t n, const double* mesh, int64_t n_mesh, double delta,
+                                      int order, int64_t M, const double* alpha, const double* W, int kind, double variance,
+                                      double lengthscale, int64_t D, double* mean, double* var, asvgp_stream_t stream) {
+  (void)handle;
+  if (!xnew || !mesh || !alpha || !W || !mean || !var || n < 0 || D < 1 || !(delta > 0.0) || !(variance > 0.0) || !(lengthscale > 0.0)) {
+    set_error("predict_deriv_1d: bad argument");
+    return ASVGP_ERR_BAD_ARG;
+  }
+  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("predict_deriv_1d: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
+  if (n_mesh != M - order + 1) { set_error("predict_deriv_1d: bad argument (n_mesh = %ld, M = %ld, order %d)", (long)n_mesh, (long)M, order); return ASVGP_ERR_BAD_ARG; }
+  if (kind != ASVGP_MATERN32 && kind != ASVGP_MATERN52) {
+    set_error("predict_deriv_1d: kernel kind %d has no mean-square derivative (only Matern-3/2 and Matern-5/2 do; Matern-1/2's k''(0) is unbounded)", kind);
+    return ASVGP_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return ASVGP_OK;
+  const double prior = (kind == ASVGP_MATERN32 ? 3.0 : 5.0 / 3.0) * variance / (lengthscale * lengthscale);
+  hipStream_t st = as_stream(stream);
+  switch (order) {
+    case 1: return launch_predict<1, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
+    case 2: return launch_predict<2, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
+    case 3: return launch_predict<3, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
+    case 4: return launch_predict<4, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
+    case 5: return launch_predict<5, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
+    default: return launch_predict<6, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
+  }
 }

@@ -69,6 +69,13 @@ class _ShardedStats:
         return self._stats
 
 
+def _require_derivative(kernel, what):
+    """f has a mean-square derivative under Matern-3/2 and 5/2 only: Matern-1/2's k''(0) is unbounded.  Raised before any launch."""
+    if kernel.kind not in (kernels.Matern32.kind, kernels.Matern52.kind):
+        raise ValueError("%s: the %s kernel has no mean-square derivative (its k''(0) is unbounded); gradient predictions need "
+                         "Matern32 or Matern52" % (what, type(kernel).__name__))
+
+
 class HostArray(np.ndarray):
     """numpy array with the one tensor method the reference's scripts call on model outputs: `.numpy()` (electricity.py:132-138:
     `model.predict_y(X)[0].numpy()`, `model.predict_log_density((X, y)).numpy()`)."""
@@ -451,6 +458,49 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         check(get_lib().asvgp_predict_cov_1d(self._h.ptr, x1.data_ptr(), n1, x2.data_ptr(), n2, b.mesh.data_ptr(), b.mesh.shape[0],
                                              b.delta_np, b.order, b.m, Wd.data_ptr(), self.kernel.kind, float(self.kernel.variance),
                                              float(self.kernel.lengthscales), cov.data_ptr(), n2, stream_ptr()), "predict_cov_1d")
+        return cov
+
+    # -- posterior of the derivative f' (not in the reference) ----------------------------------------------------------------
+    def predict_f_gradient_device(self, Xnew):
+        """Posterior of the slope f'(x): mean (n, D) and variance (n, 1) as device tensors, one streaming kernel (asvgp_predict_deriv_1d):
+        mean = phi'^T alpha, var = c v / l^2 + phi'^T W phi' with predict_f's alpha and band W (the same _posterior cache)."""
+        _require_derivative(self.kernel, "GPR_1d.predict_f_gradient_device")
+        alpha, W = self._posterior()
+        b = self.basis
+        x = _to_device(Xnew, self._stats.device).reshape(-1)
+        n = x.shape[0]
+        mean = torch.empty((n, self.D), dtype=torch.float64, device=x.device)
+        var = torch.empty((n, 1), dtype=torch.float64, device=x.device)
+        check(get_lib().asvgp_predict_deriv_1d(self._h.ptr, x.data_ptr(), n, b.mesh.data_ptr(), b.mesh.shape[0], b.delta_np, b.order, b.m,
+                                               alpha.data_ptr(), W.data_ptr(), self.kernel.kind, float(self.kernel.variance),
+                                               float(self.kernel.lengthscales), self.D, mean.data_ptr(), var.data_ptr(), stream_ptr()),
+              "predict_deriv_1d")
+        return mean, var
+
+    def predict_f_gradient(self, Xnew):
+        """predict_f_gradient_device as numpy: (mean (n, D), var (n, 1)) of f'(Xnew)."""
+        mean, var = self.predict_f_gradient_device(Xnew)
+        return mean.cpu().numpy(), var.cpu().numpy()
+
+    def predict_f_gradient_cov_device(self, X1, X2=None, derivs=(1, 1)):
+        """cov[f^(p)(X1), f^(q)(X2)] (n1, n2) as a device tensor, (p, q) = derivs in {0, 1}^2; X2=None means X1 against itself.
+        d_x^p d_x'^q k(x, x') + phi^(p)(x)^T (P^-1 - Kuu^-1) phi^(q)(x') from predict_f_cov_device's cached W_dense
+        (asvgp_predict_cov_deriv_1d); derivs=(0, 0) is predict_f_cov_device."""
+        p, q = (int(d) for d in derivs)
+        if p not in (0, 1) or q not in (0, 1):
+            raise ValueError("GPR_1d.predict_f_gradient_cov_device: derivs must be in {0, 1}^2, got %r" % (tuple(derivs),))
+        if p or q:
+            _require_derivative(self.kernel, "GPR_1d.predict_f_gradient_cov_device")
+        Wd = self._posterior_cov()
+        b = self.basis
+        x1 = _to_device(X1, self._stats.device).reshape(-1)
+        x2 = x1 if X2 is None else _to_device(X2, self._stats.device).reshape(-1)
+        n1, n2 = x1.shape[0], x2.shape[0]
+        cov = torch.empty((n1, n2), dtype=torch.float64, device=x1.device)
+        check(get_lib().asvgp_predict_cov_deriv_1d(self._h.ptr, x1.data_ptr(), n1, x2.data_ptr(), n2, b.mesh.data_ptr(), b.mesh.shape[0],
+                                                   b.delta_np, b.order, b.m, Wd.data_ptr(), self.kernel.kind, float(self.kernel.variance),
+                                                   float(self.kernel.lengthscales), p, q, cov.data_ptr(), n2, stream_ptr()),
+              "predict_cov_deriv_1d")
         return cov
 
     def predict_f_full_cov(self, Xnew):
@@ -1286,6 +1336,38 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
                                                  float(k2.variance), float(k2.lengthscales), cov.data_ptr(), n2, stream_ptr()),
               "predict_cov_kron2d")
         return cov
+
+    def predict_f_gradient_device(self, Xnew):
+        """Posterior of the gradient of f at Xnew (n, 2): mean (n, 2) and covariance (n, 2, 2) as device tensors, one per-point kernel
+        (asvgp_predict_grad_kron2d) on predict_f_device's factor and selected inverse (_post), in whichever layout _twist_layout() chose.
+        cov[:, i, j] = Cov[d_i f, d_j f] = [i = j] c_i v_i / l_i^2 v_other + psi_i^T P^-1 psi_j - (phi1^(a)T K1^-1 phi1^(b))(phi2^(c)T K2^-1 phi2^(d))."""
+        self._require_2d("predict_f_gradient_device")
+        for i, kern in enumerate(self.kernels):
+            _require_derivative(kern, "GPR_kron.predict_f_gradient_device (dimension %d)" % i)
+        key, lay = self.theta(), self._twist_layout()
+        if self._post is None or self._post[0] != key or self._post[1].get("twist") != lay:
+            f = self._factor(want_alpha=False)
+            self._post = (key, f, self._selinv(f))               # (also fills f["alpha"])
+        f, (SigD, SigS, Bb) = self._post[1], self._post[2]
+        b1, b2 = self.bases
+        k1, k2 = self.kernels
+        X = _to_device(Xnew, self._stats.device).reshape(-1, 2).contiguous()
+        n = X.shape[0]
+        mean = torch.empty((n, 2), dtype=torch.float64, device=X.device)
+        c3 = torch.empty((n, 3), dtype=torch.float64, device=X.device)
+        lay = f.get("twist")
+        layout = (0, -(-self.Mtot // Bb), 0, 0, 0) if lay is None else (1, lay["nb"], lay["top_end"], lay["padt"], lay["padb"])
+        check(get_lib().asvgp_predict_grad_kron2d(X.data_ptr(), n, b1.mesh.data_ptr(), b1.mesh.shape[0], b1.delta_np, b1.m, b2.mesh.data_ptr(),
+                                                  b2.mesh.shape[0], b2.delta_np, b2.m, self.order, f["alpha"].data_ptr(), f["Ss"][0].data_ptr(),
+                                                  f["Ss"][1].data_ptr(), SigD.data_ptr(), SigS.data_ptr(), Bb, *layout, k1.kind,
+                                                  float(k1.variance), float(k1.lengthscales), k2.kind, float(k2.variance),
+                                                  float(k2.lengthscales), mean.data_ptr(), c3.data_ptr(), stream_ptr()), "predict_grad_kron2d")
+        return mean, c3[:, [0, 1, 1, 2]].reshape(n, 2, 2)
+
+    def predict_f_gradient(self, Xnew):
+        """predict_f_gradient_device as numpy: (mean (n, 2), cov (n, 2, 2))."""
+        mean, cov = self.predict_f_gradient_device(Xnew)
+        return mean.cpu().numpy(), cov.cpu().numpy()
 
     def predict_f_full_cov(self, Xnew):
         """numpy (mean (n, 1), cov (1, n, n)): gpflow's predict_f(full_cov=True) layout, cov a read-only broadcast."""

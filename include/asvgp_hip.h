@@ -344,6 +344,25 @@ int asvgp_predict_cov_1d(asvgp_handle_t handle, const double* x1, int64_t n1, co
                          double lengthscale, double* cov, int64_t ldc, asvgp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Posterior of the derivative f' (GPR_1d.predict_f_gradient_device / predict_f_gradient_cov_device; not in the reference)
+ * The derivative of a GP is a GP: with phi' = dphi/dx = (1/delta) d/dt of the B-spline pieces,
+ * predict_deriv: per test point mean[p * D + d] = phi'^T alpha[:, d], var[p] = c v / l^2 + phi'^T W phi' (c = 3 for Matern-3/2,
+ * 5/3 for Matern-5/2; alpha and band W of asvgp_posterior_prepare_1d).  The plan of asvgp_predict_1d's table kernel (LDS staging for
+ * D = 1 and n >= 65 536, two points per lane with 16-byte-aligned buffers).
+ * predict_cov_deriv: cov[a * ldc + b] = cov[f^(p)(x1_a), f^(q)(x2_b)] = d_x^p d_x'^q k(x1_a, x2_b) + phi^(p)(x1_a)^T W_dense phi^(q)(x2_b),
+ * p, q in {0, 1}; (0, 0) is asvgp_predict_cov_1d (the same kernel).  W_dense of asvgp_posterior_cov_prepare_1d.
+ * Both: ASVGP_ERR_BAD_ARG for a NULL pointer, a negative size, ldc < n2, n_mesh != M - order + 1 or p, q outside {0, 1};
+ * ASVGP_ERR_UNSUPPORTED for order outside 1..6, an unknown kind, or Matern-1/2 when a derivative is asked for (k''(0) is unbounded:
+ * f has no mean-square derivative).  n = 0: ASVGP_OK, nothing launched.  The handle may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+int asvgp_predict_deriv_1d(asvgp_handle_t handle, const double* xnew, int64_t n, const double* mesh, int64_t n_mesh, double delta,
+                           int order, int64_t M, const double* alpha, const double* W, int kind, double variance, double lengthscale,
+                           int64_t D, double* mean, double* var, asvgp_stream_t stream);
+int asvgp_predict_cov_deriv_1d(asvgp_handle_t handle, const double* x1, int64_t n1, const double* x2, int64_t n2, const double* mesh,
+                               int64_t n_mesh, double delta, int order, int64_t M, const double* W_dense, int kind, double variance,
+                               double lengthscale, int p, int q, double* cov, int64_t ldc, asvgp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 2-D Kronecker (tensor-product) path   replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
  * linear algebra of GPR_kron gpr.py:239-359 (KufKfu.todense(), tf.linalg.cholesky / triangular_solve / cholesky_solve).
  * Basis pair (i1, i2) has row index i1*m2 + i2 (dim-0 major, as make_kvs_two_sparse).  Both bases share `order` = k
@@ -442,6 +461,23 @@ int asvgp_predict_kron2d_var_twisted(const double* Xnew, int64_t n, const double
                                      const double* mesh2, int64_t n_mesh2, double delta2, int64_t m1, int64_t m2, int order,
                                      const double* SigD, const double* SigS, int64_t Bb, int64_t nb, int64_t top_end, int64_t padt,
                                      int64_t padb, double* qp, asvgp_stream_t stream);
+/* Posterior gradient of the 2-D model (GPR_kron.predict_f_gradient_device; not in the reference), per test point, with
+ * psi_1 = phi1' (x) phi2, psi_2 = phi1 (x) phi2', Sigma = P^-1, S_d = band(K_d^-1):
+ *   mean2[2p + i] = psi_i^T alpha,
+ *   cov3[3p + (0, 1, 2)] = (C_11, C_12, C_22),  C_ij = [i = j] c_i v_i / l_i^2 v_other + psi_i^T Sigma psi_j
+ *                                                       - (phi1^(a)T S1 phi1^(b))(phi2^(c)T S2 phi2^(d)),
+ * (a, b, c, d) = (1, 1, 0, 0), (1, 0, 0, 1), (0, 0, 1, 1); c = 3 (Matern-3/2) or 5/3 (Matern-5/2).  Every entry lies in the point's
+ * (k+1)^2 window, so the selected inverse (SigD / SigS) is enough.  Layout as asvgp_kron_dense_inverse: twisted = 0 one-sided
+ * (nb, top_end, padt, padb ignored), twisted = 1 the layout of asvgp_kron_assemble_twisted.  X (n, 2) row-major, 16-byte aligned;
+ * alpha (M_tot); S1, S2 lower bands (k+1, m_d).  ASVGP_ERR_BAD_ARG for a NULL pointer, a negative size, n_mesh_d != m_d - order + 1,
+ * Bb below the bandwidth k m2 + k, an inconsistent twisted layout or an unaligned X; ASVGP_ERR_UNSUPPORTED for order outside 1..6 and
+ * for a Matern-1/2 or unknown kind in either dimension.  n = 0: ASVGP_OK, nothing launched. */
+int asvgp_predict_grad_kron2d(const double* X, int64_t n, const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
+                              const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order, const double* alpha,
+                              const double* S1, const double* S2, const double* SigD, const double* SigS, int64_t Bb, int twisted,
+                              int64_t nb, int64_t top_end, int64_t padt, int64_t padb, int kind1, double variance1,
+                              double lengthscale1, int kind2, double variance2, double lengthscale2, double* mean2, double* cov3,
+                              asvgp_stream_t stream);
 
 /* Full posterior covariance of the 2-D model (GPR_kron.predict_f_cov_device; the reference's predict_f(full_cov=True) raises):
  *   cov[f(x), f(x')] = k1(x_1, x'_1) k2(x_2, x'_2) + phi(x)^T Sigma phi(x') - (phi1^T K1^-1 phi1')(phi2^T K2^-1 phi2'),  Sigma = P^-1.
