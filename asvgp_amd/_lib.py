@@ -82,6 +82,8 @@ SIGNATURES = {
     "asvgp_predict_cov_kron2d": (_I, [_P, _P, _L, _P, _L, _P, _L, _D, _L, _P, _L, _D, _L, _I, _P, _P, _P, _I, _D, _D, _I, _D, _D, _P, _L, _P]),
     "asvgp_predict_cov_additive": (_I, [_P, _P, _L, _P, _L, _I, _P, _c.POINTER(_L), _c.POINTER(_D), _c.POINTER(_L), _I,
                                          _c.POINTER(_I), _c.POINTER(_D), _c.POINTER(_D), _P, _P, _L, _P]),
+    "asvgp_predict_components_additive": (_I, [_P, _P, _L, _I, _P, _c.POINTER(_L), _c.POINTER(_D), _c.POINTER(_L), _I, _c.POINTER(_I),
+                                                _c.POINTER(_D), _c.POINTER(_D), _I, _P, _P, _P, _P, _P]),
     "asvgp_profile_enable": (_I, [_P, _I]),
     "asvgp_profile_read": (_I, [_P, _c.POINTER(_D), _c.POINTER(_L)]),
     "asvgp_kron_stats_doubles": (_Z, [_L, _L, _I]),

@@ -5,6 +5,13 @@
 // posterior_cov.hip); the x2 points are swept across the lanes, and for every one of them each dimension's cell and k + 1 B-spline
 // weights are contracted with k + 1 LDS reads of g_a per row, that dimension's Matern closed form added in fp64, and the rows of cov
 // stored coalesced.  The per-dimension scalars travel in a by-value kernel argument (no copy, no allocation, no per-handle state).
+//
+// Components and gradient (asvgp_predict_components_additive), per point a and dimensions i, j, derivative order p in {0, 1}:
+//   mean[a, i] = phi_i^(p)(x_ai)^T alpha_i,   cov[a, i, j] = [i = j] prior_i + phi_i^(p)(x_ai)^T W_ij phi_j^(p)(x_aj)
+// One point per thread: for every pair j <= i the (k + 1) x (k + 1) block of W at the two cells is gathered into registers (k + 1 row
+// segments of k + 1 contiguous doubles, 64-bit offsets) and contracted with both weight vectors; W is read in place, so M_tot has no LDS
+// limit.  The loops over i and j are rolled and dimension j's cell and weights re-evaluated inside the j loop, so that no register array
+// is indexed by a runtime index.
 #include "asvgp_common.hpp"
 
 namespace asvgp {
@@ -22,6 +29,52 @@ struct AddDims {
   int kind[ASVGP_ADDITIVE_COV_MAX_D];
   double inv_delta[ASVGP_ADDITIVE_COV_MAX_D], v[ASVGP_ADDITIVE_COV_MAX_D], inv_l[ASVGP_ADDITIVE_COV_MAX_D];
 };
+
+// the per-dimension checks both entry points share (what: the entry point's name in the error text)
+static int check_additive_dims(const char* what, int d, const int64_t* n_mesh, const double* delta, const int64_t* m, int order,
+                               const int* kind, const double* variance, const double* lengthscale) {
+  if (d > ASVGP_ADDITIVE_COV_MAX_D) {
+    set_error("%s: d = %d above the maximum %d", what, d, (int)ASVGP_ADDITIVE_COV_MAX_D);
+    return ASVGP_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < d; ++i)
+    if (!(delta[i] > 0.0) || !(variance[i] > 0.0) || !(lengthscale[i] > 0.0)) {
+      set_error("%s: bad argument (dimension %d: delta %g, variance %g, lengthscale %g)", what, i, delta[i], variance[i], lengthscale[i]);
+      return ASVGP_ERR_BAD_ARG;
+    }
+  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("%s: order %d unsupported", what, order); return ASVGP_ERR_UNSUPPORTED; }
+  for (int i = 0; i < d; ++i)
+    if (kind[i] < ASVGP_MATERN12 || kind[i] > ASVGP_MATERN52) {
+      set_error("%s: kernel kind %d of dimension %d unsupported", what, kind[i], i);
+      return ASVGP_ERR_UNSUPPORTED;
+    }
+  for (int i = 0; i < d; ++i)
+    if (m[i] < order + 1 || n_mesh[i] != m[i] - order + 1) {
+      set_error("%s: bad argument (dimension %d: n_mesh = %ld, m = %ld, order %d)", what, i, (long)n_mesh[i], (long)m[i], order);
+      return ASVGP_ERR_BAD_ARG;
+    }
+  return ASVGP_OK;
+}
+
+// the kernel argument of both entry points (the checks above passed, and M_tot fits an int)
+static AddDims make_dims(int d, const int64_t* n_mesh, const double* delta, const int64_t* m, const int* kind, const double* variance,
+                         const double* lengthscale) {
+  AddDims P;
+  P.d = d;
+  int mesh_off = 0, off = 0;
+  for (int i = 0; i < ASVGP_ADDITIVE_COV_MAX_D; ++i) {
+    const bool on = i < d;
+    P.mesh_off[i] = on ? mesh_off : 0;
+    P.n_mesh[i] = on ? (int)n_mesh[i] : 0;
+    P.off[i] = on ? off : 0;
+    P.kind[i] = on ? kind[i] : 0;
+    P.inv_delta[i] = on ? 1.0 / delta[i] : 0.0;
+    P.v[i] = on ? variance[i] : 0.0;
+    P.inv_l[i] = on ? 1.0 / lengthscale[i] : 0.0;
+    if (on) { mesh_off += (int)n_mesh[i]; off += (int)m[i]; }
+  }
+  return P;
+}
 
 // k(x, x') of gpflow's Matern kernels, r = |x - x'| / l (the closed form of posterior_cov.hip)
 __device__ __forceinline__ double matern_a(int kind, double v, double inv_l, double x, double y) {
@@ -120,6 +173,78 @@ static int launch_cov_additive(const double* x1, long n1, const double* x2, long
   return check_launch("predict_cov_additive");
 }
 
+constexpr int CC_THREADS = 256;
+
+// the cell of x in dimension i and its k + 1 weights phi_i^(p) (x), times (1 / delta_i)^p; returns the row of w[0] (rows row - r, r = 0..K)
+template <int K, int P>
+__device__ __forceinline__ long cell_weights(const double* __restrict__ meshes, const AddDims& D, int i, double x, double (&w)[K + 1]) {
+  const double* mesh = meshes + D.mesh_off[i];
+  const double inv_delta = D.inv_delta[i];
+  const int idx = neighbour_index(x, mesh, D.n_mesh[i], mesh[0], inv_delta);
+  bspline_pieces<K, P>((x - mesh[idx]) * inv_delta, w);
+  if (P) {
+#pragma unroll
+    for (int r = 0; r <= K; ++r) w[r] *= inv_delta;
+  }
+  return (long)D.off[i] + idx + K;
+}
+
+template <int K, int P>
+__global__ __launch_bounds__(CC_THREADS) void predict_components_additive_kernel(const double* __restrict__ X, long n,
+                                                                                 const double* __restrict__ meshes, AddDims D, long M,
+                                                                                 const double* __restrict__ alpha,
+                                                                                 const double* __restrict__ W, double* __restrict__ mean,
+                                                                                 double* __restrict__ cov) {
+  const long a = (long)blockIdx.x * CC_THREADS + threadIdx.x;
+  if (a >= n) return;
+  const int d = D.d;
+  const double* x = X + a * d;
+  double* cov_a = cov + a * d * d;
+  for (int i = 0; i < d; ++i) {
+    double wi[K + 1];
+    const long ri = cell_weights<K, P>(meshes, D, i, x[i], wi);
+    double mu = 0.0;
+#pragma unroll
+    for (int r = 0; r <= K; ++r) mu = fma(wi[r], alpha[ri - r], mu);
+    mean[a * d + i] = mu;
+    for (int j = 0; j <= i; ++j) {
+      double wj[K + 1];
+      const long cj = cell_weights<K, P>(meshes, D, j, x[j], wj);
+      double blk[K + 1][K + 1];                      // blk[r][s] = W[ri - r, cj - s]: every load issued before the first use
+#pragma unroll
+      for (int r = 0; r <= K; ++r) {
+        const double* row = W + (ri - r) * M + cj - K;
+#pragma unroll
+        for (int s = 0; s <= K; ++s) blk[r][s] = row[K - s];
+      }
+      double q = 0.0;
+#pragma unroll
+      for (int r = 0; r <= K; ++r) {
+        double t = 0.0;
+#pragma unroll
+        for (int s = 0; s <= K; ++s) t = fma(blk[r][s], wj[s], t);
+        q = fma(wi[r], t, q);
+      }
+      if (j == i) {
+        const double v = D.v[i], il = D.inv_l[i];
+        q += P == 0 ? v : (D.kind[i] == ASVGP_MATERN32 ? 3.0 : 5.0 / 3.0) * v * il * il;
+      }
+      cov_a[i * d + j] = q;                          // (one value for both halves: symmetric bit for bit)
+      cov_a[j * d + i] = q;
+    }
+  }
+}
+
+template <int K>
+static int launch_components_additive(const double* X, long n, const double* meshes, const AddDims& D, long M, int deriv,
+                                      const double* alpha, const double* W, double* mean, double* cov, hipStream_t st) {
+  const long gx = (n + CC_THREADS - 1) / CC_THREADS;
+  if (gx > 0x7fffffff) { set_error("predict_components_additive: n = %ld too large for one launch", n); return ASVGP_ERR_UNSUPPORTED; }
+  auto kern = deriv ? predict_components_additive_kernel<K, 1> : predict_components_additive_kernel<K, 0>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(CC_THREADS), 0, st, X, n, meshes, D, M, alpha, W, mean, cov);
+  return check_launch("predict_components_additive");
+}
+
 }  // namespace asvgp
 
 using namespace asvgp;
@@ -135,27 +260,7 @@ extern "C" int asvgp_predict_cov_additive(asvgp_handle_t handle, const double* x
     set_error("predict_cov_additive: bad argument");
     return ASVGP_ERR_BAD_ARG;
   }
-  if (d > ASVGP_ADDITIVE_COV_MAX_D) {
-    set_error("predict_cov_additive: d = %d above the maximum %d", d, (int)ASVGP_ADDITIVE_COV_MAX_D);
-    return ASVGP_ERR_UNSUPPORTED;
-  }
-  for (int i = 0; i < d; ++i)
-    if (!(delta[i] > 0.0) || !(variance[i] > 0.0) || !(lengthscale[i] > 0.0)) {
-      set_error("predict_cov_additive: bad argument (dimension %d: delta %g, variance %g, lengthscale %g)", i, delta[i], variance[i],
-                lengthscale[i]);
-      return ASVGP_ERR_BAD_ARG;
-    }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("predict_cov_additive: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  for (int i = 0; i < d; ++i)
-    if (kind[i] < ASVGP_MATERN12 || kind[i] > ASVGP_MATERN52) {
-      set_error("predict_cov_additive: kernel kind %d of dimension %d unsupported", kind[i], i);
-      return ASVGP_ERR_UNSUPPORTED;
-    }
-  for (int i = 0; i < d; ++i)
-    if (m[i] < order + 1 || n_mesh[i] != m[i] - order + 1) {
-      set_error("predict_cov_additive: bad argument (dimension %d: n_mesh = %ld, m = %ld, order %d)", i, (long)n_mesh[i], (long)m[i], order);
-      return ASVGP_ERR_BAD_ARG;
-    }
+  if (int st = check_additive_dims("predict_cov_additive", d, n_mesh, delta, m, order, kind, variance, lengthscale)) return st;
   size_t M = 0;
   bool huge = false;                                 // (an m_i alone beyond the plan: the sum is not formed, so it cannot overflow)
   for (int i = 0; i < d; ++i) {
@@ -168,20 +273,7 @@ extern "C" int asvgp_predict_cov_additive(asvgp_handle_t handle, const double* x
     return ASVGP_ERR_UNSUPPORTED;
   }
   if (n1 == 0 || n2 == 0) return ASVGP_OK;
-  AddDims P;
-  P.d = d;
-  int mesh_off = 0, off = 0;
-  for (int i = 0; i < ASVGP_ADDITIVE_COV_MAX_D; ++i) {
-    const bool on = i < d;
-    P.mesh_off[i] = on ? mesh_off : 0;
-    P.n_mesh[i] = on ? (int)n_mesh[i] : 0;
-    P.off[i] = on ? off : 0;
-    P.kind[i] = on ? kind[i] : 0;
-    P.inv_delta[i] = on ? 1.0 / delta[i] : 0.0;
-    P.v[i] = on ? variance[i] : 0.0;
-    P.inv_l[i] = on ? 1.0 / lengthscale[i] : 0.0;
-    if (on) { mesh_off += (int)n_mesh[i]; off += (int)m[i]; }
-  }
+  const AddDims P = make_dims(d, n_mesh, delta, m, kind, variance, lengthscale);
   hipStream_t st = as_stream(stream);
   const int Mt = (int)M;
   switch (order) {
@@ -191,5 +283,45 @@ extern "C" int asvgp_predict_cov_additive(asvgp_handle_t handle, const double* x
     case 4: return launch_cov_additive<4>(x1, n1, x2, n2, meshes, P, Mt, W, cov, ldc, st);
     case 5: return launch_cov_additive<5>(x1, n1, x2, n2, meshes, P, Mt, W, cov, ldc, st);
     default: return launch_cov_additive<6>(x1, n1, x2, n2, meshes, P, Mt, W, cov, ldc, st);
+  }
+}
+
+// components (deriv = 0) or gradient (deriv = 1) of the additive posterior, per point: mean (n, d), cov (n, d, d)
+extern "C" int asvgp_predict_components_additive(asvgp_handle_t handle, const double* X, int64_t n, int d, const double* meshes,
+                                                 const int64_t* n_mesh, const double* delta, const int64_t* m, int order, const int* kind,
+                                                 const double* variance, const double* lengthscale, int deriv, const double* alpha,
+                                                 const double* W, double* mean, double* cov, asvgp_stream_t stream) {
+  (void)handle;
+  if (!X || !meshes || !n_mesh || !delta || !m || !kind || !variance || !lengthscale || !alpha || !W || !mean || !cov || n < 0 ||
+      d < 1 || deriv < 0 || deriv > 1) {
+    set_error("predict_components_additive: bad argument");
+    return ASVGP_ERR_BAD_ARG;
+  }
+  if (int st = check_additive_dims("predict_components_additive", d, n_mesh, delta, m, order, kind, variance, lengthscale)) return st;
+  if (deriv)
+    for (int i = 0; i < d; ++i)
+      if (kind[i] == ASVGP_MATERN12) {
+        set_error("predict_components_additive: dimension %d is Matern-1/2, which has no mean-square derivative (its k''(0) is unbounded); "
+                  "the gradient needs Matern-3/2 or Matern-5/2", i);
+        return ASVGP_ERR_UNSUPPORTED;
+      }
+  int64_t M = 0;                                     // (M_tot, and the smaller mesh offsets, travel as int)
+  for (int i = 0; i < d; ++i) {
+    if (m[i] > 0x7fffffff - M) {
+      set_error("predict_components_additive: M_tot above 2^31 - 1 (dimension %d: m = %ld)", i, (long)m[i]);
+      return ASVGP_ERR_UNSUPPORTED;
+    }
+    M += m[i];
+  }
+  if (n == 0) return ASVGP_OK;
+  const AddDims P = make_dims(d, n_mesh, delta, m, kind, variance, lengthscale);
+  hipStream_t st = as_stream(stream);
+  switch (order) {
+    case 1: return launch_components_additive<1>(X, n, meshes, P, M, deriv, alpha, W, mean, cov, st);
+    case 2: return launch_components_additive<2>(X, n, meshes, P, M, deriv, alpha, W, mean, cov, st);
+    case 3: return launch_components_additive<3>(X, n, meshes, P, M, deriv, alpha, W, mean, cov, st);
+    case 4: return launch_components_additive<4>(X, n, meshes, P, M, deriv, alpha, W, mean, cov, st);
+    case 5: return launch_components_additive<5>(X, n, meshes, P, M, deriv, alpha, W, mean, cov, st);
+    default: return launch_components_additive<6>(X, n, meshes, P, M, deriv, alpha, W, mean, cov, st);
   }
 }

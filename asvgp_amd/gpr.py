@@ -1496,6 +1496,7 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
         self._info = torch.zeros(1, dtype=torch.int32, device=dev)
         self._dense = None
         self._post_cov = None                 # (key, W, concatenated meshes) of predict_f_cov_device
+        self._post_alpha = None               # (key, alpha = P^-1 Kuf y / sigma2) from the factor W came from
 
     # ------------------------------------------------------------------------------------------------------
     def _phi_pass_local(self):
@@ -1516,6 +1517,7 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
                                          stream_ptr()), "phi_cross_2d")
         self._dense = None
         self._post_cov = None                 # (W was built from the statistics just replaced)
+        self._post_alpha = None
         return self._stats
 
     def _band(self, i):
@@ -1708,16 +1710,19 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
     def _posterior_cov(self):
         """W = P^-1 - blockdiag(K_1^-1 .. K_d^-1) (M_tot x M_tot, device) once per theta: cholesky_inverse of the dense factor of
         _factor, then each dimension's dense K_i^-1 (torch cholesky_inverse of the m_i x m_i Kuu band) subtracted from its block.
-        Cached on _post_cov with the concatenated meshes; _phi_pass_local and close() drop it."""
+        Cached on _post_cov with the concatenated meshes; alpha = P^-1 Kuf y / sigma2 (M_tot), from the same factor, on _post_alpha under
+        the same key.  _phi_pass_local and close() drop both."""
         v, s = self.theta()
         key = (tuple(v), s)
-        if self._post_cov is not None and self._post_cov[0] == key:
+        if self._post_cov is not None and self._post_cov[0] == key and self._post_alpha is not None and self._post_alpha[0] == key:
             return self._post_cov[1], self._post_cov[2]
-        self._post_cov = None
+        self._post_cov = self._post_alpha = None
         f = self._factor()
+        alpha = torch.linalg.solve_triangular(f["L"].t(), f["c"], upper=True).reshape(-1).contiguous()   # L^-T (L^-1 Kuf y / s)
         W = self._minus_kuu_inverse(torch.cholesky_inverse(f["L"]), f["Ks"])
         meshes = torch.cat([bs.mesh.reshape(-1) for bs in self.bases]).contiguous()
         self._post_cov = (key, W, meshes)
+        self._post_alpha = (key, alpha)
         return W, meshes
 
     def _minus_kuu_inverse(self, W, Ks):
@@ -1770,9 +1775,58 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
         this model's predict_f_device / predict_f_cov_device (same seed and jitter semantics, NotPositiveDefiniteError alike)."""
         return GPR_1d.predict_f_samples(self, Xnew, num_samples, full_cov, jitter, seed)
 
+    # -- components f_i(x_i) and gradient d f / d x_i = f_i'(x_i) (not in the reference: its predict_f returns the sum) ---------------
+    def _predict_components(self, Xnew, deriv, what):
+        """mean (n, d) and cov (n, d, d) of phi_i^(p)(x_i) against alpha and W (asvgp_predict_components_additive), p = deriv."""
+        if deriv:
+            for i, kern in enumerate(self.kernels):
+                _require_derivative(kern, "%s (dimension %d)" % (what, i))
+        dev, d = self._stats.device, self.d
+        X = _to_device(Xnew, dev).reshape(-1, d).contiguous()
+        n = X.shape[0]
+        mean = torch.empty((n, d), dtype=torch.float64, device=dev)
+        cov = torch.empty((n, d, d), dtype=torch.float64, device=dev)
+        if n == 0:
+            return mean, cov
+        W, meshes = self._posterior_cov()
+        alpha = self._post_alpha[1]
+        arr = lambda t, vals: (t * d)(*vals)
+        check(get_lib().asvgp_predict_components_additive(None, X.data_ptr(), n, d, meshes.data_ptr(),
+                                                          arr(ctypes.c_int64, [bs.mesh.shape[0] for bs in self.bases]),
+                                                          arr(ctypes.c_double, [bs.delta_np for bs in self.bases]),
+                                                          arr(ctypes.c_int64, [bs.m for bs in self.bases]), self.bandwidth,
+                                                          arr(ctypes.c_int, [kn.kind for kn in self.kernels]),
+                                                          arr(ctypes.c_double, [float(kn.variance) for kn in self.kernels]),
+                                                          arr(ctypes.c_double, [float(kn.lengthscales) for kn in self.kernels]), deriv,
+                                                          alpha.data_ptr(), W.data_ptr(), mean.data_ptr(), cov.data_ptr(), stream_ptr()),
+              "predict_components_additive")
+        return mean, cov
+
+    def predict_f_components_device(self, Xnew):
+        """Posterior of the additive components f_i(x_i) at Xnew (n, d): mean (n, d) and covariance (n, d, d) as device tensors,
+        cov[:, i, j] = Cov[f_i(x_i), f_j(x_j)] = [i = j] v_i + phi_i^T W_ij phi_j, from predict_f_cov_device's cached W and alpha.
+        Summed over i (and i, j) they give predict_f's mean (and variance).  Every Matern."""
+        return self._predict_components(Xnew, 0, "GPR_additive.predict_f_components_device")
+
+    def predict_f_components(self, Xnew):
+        """predict_f_components_device as numpy: (mean (n, d), cov (n, d, d))."""
+        mean, cov = self.predict_f_components_device(Xnew)
+        return mean.cpu().numpy(), cov.cpu().numpy()
+
+    def predict_f_gradient_device(self, Xnew):
+        """Posterior of the gradient of f at Xnew (n, d): mean (n, d) and covariance (n, d, d) as device tensors, d f / d x_i = f_i'(x_i),
+        cov[:, i, j] = [i = j] c_i v_i / l_i^2 + phi_i'^T W_ij phi_j' (c = 3 for Matern-3/2, 5/3 for Matern-5/2).  A Matern-1/2 dimension
+        raises ValueError before anything is built or launched."""
+        return self._predict_components(Xnew, 1, "GPR_additive.predict_f_gradient_device")
+
+    def predict_f_gradient(self, Xnew):
+        """predict_f_gradient_device as numpy: (mean (n, d), cov (n, d, d))."""
+        mean, cov = self.predict_f_gradient_device(Xnew)
+        return mean.cpu().numpy(), cov.cpu().numpy()
+
     def close(self):
-        """Also releases the cached dense W."""
-        self._post_cov = None
+        """Also releases the cached dense W and alpha."""
+        self._post_cov = self._post_alpha = None
         super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):

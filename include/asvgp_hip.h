@@ -523,6 +523,21 @@ int asvgp_predict_cov_additive(asvgp_handle_t handle, const double* x1, int64_t 
                                const int* kind, const double* variance, const double* lengthscale, const double* W, double* cov,
                                int64_t ldc, asvgp_stream_t stream);
 
+/* Posterior of the additive components and of the gradient (GPR_additive.predict_f_components_device / predict_f_gradient_device;
+ * not in the reference: its predict_f returns the sum only), per test point a and dimensions i, j < d, derivative order p = deriv:
+ *   mean[a * d + i]          = phi_i^(p)(x[a, i])^T alpha_i,
+ *   cov[(a * d + i) * d + j] = [i = j] prior_i + phi_i^(p)(x[a, i])^T W_ij phi_j^(p)(x[a, j]),
+ * prior_i = v_i (p = 0) or c_i v_i / l_i^2 (p = 1; c = 3 for Matern-3/2, 5/3 for Matern-5/2); phi^(1) = d phi / dx.  p = 0 gives the
+ * components f_i(x_i), p = 1 the gradient d f / d x_i = f_i'(x_i).  alpha = P^-1 Kuf y / sigma^2 (M_tot) and W (M_tot x M_tot, symmetric)
+ * as in asvgp_predict_cov_additive; x (n, d) row-major; mean (n, d), cov (n, d, d) row-major and symmetric bit for bit.  The host
+ * arrays and their checks are asvgp_predict_cov_additive's; W is read in place (no LDS staging, no limit on M_tot).  Also
+ * ASVGP_ERR_BAD_ARG for a NULL alpha / mean or deriv outside {0, 1}; ASVGP_ERR_UNSUPPORTED for deriv = 1 with a Matern-1/2 dimension
+ * (no mean-square derivative).  n = 0: ASVGP_OK, nothing launched.  The handle may be NULL. */
+int asvgp_predict_components_additive(asvgp_handle_t handle, const double* X, int64_t n, int d, const double* meshes,
+                                      const int64_t* n_mesh, const double* delta, const int64_t* m, int order, const int* kind,
+                                      const double* variance, const double* lengthscale, int deriv, const double* alpha,
+                                      const double* W, double* mean, double* cov, asvgp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, HIP events are recorded on the launch stream immediately around
  * every Phi-pass kernel launch (up to 1024 launches); asvgp_profile_read synchronises on them and returns the
