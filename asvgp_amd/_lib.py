@@ -19,6 +19,11 @@ SIGNATURES = {
     "asvgp_create": (_I, [_c.POINTER(_P)]),
     "asvgp_destroy": (_I, [_P]),
     "asvgp_phi_accumulate_1d": (_I, [_P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _Z, _P]),
+    "asvgp_phi_weighted_workspace_bytes": (_Z, [_L, _I, _L]),
+    "asvgp_phi_accumulate_1d_weighted": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _P, _Z, _P]),
+    "asvgp_set_weight_sums": (_I, [_P, _D, _D, _D]),
+    "asvgp_phi_accumulate_kron2d_weighted": (_I, [_P, _P, _P, _L, _P, _L, _D, _L, _P, _L, _D, _L, _I, _P, _P, _P]),
+    "asvgp_phi_accumulate_kron2d_sorted_weighted": (_I, [_P, _P, _P, _L, _P, _P, _L, _D, _L, _P, _L, _D, _L, _I, _P, _P, _P]),
     "asvgp_set_phi_algorithm": (_I, [_P, _I]),
     "asvgp_phi_last_algorithm": (_I, [_P]),
     "asvgp_set_phi_input_order": (_I, [_P, _I]),
@@ -186,6 +191,13 @@ class Handle:
 
     def set_phi_algorithm(self, algo):
         check(self._lib.asvgp_set_phi_algorithm(self.ptr, int(algo)), "set_phi_algorithm")
+
+    def set_weight_sums(self, n_pos, sum_w, sum_log_w):
+        """asvgp_set_weight_sums: [N+, sum w, sum log w] of a weighted model - the fused ELBO launches evaluate the weighted bound from
+        them; n_pos < 0 (or None) returns the handle to the unweighted bound."""
+        if n_pos is None:
+            n_pos, sum_w, sum_log_w = -1.0, 0.0, 0.0
+        check(self._lib.asvgp_set_weight_sums(self.ptr, float(n_pos), float(sum_w), float(sum_log_w)), "set_weight_sums")
 
     def phi_last_algorithm(self):
         return int(self._lib.asvgp_phi_last_algorithm(self.ptr))

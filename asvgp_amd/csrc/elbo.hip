@@ -101,7 +101,7 @@ struct KuuInterior { double k[8]; long lo, hi; double bnd[2 * PRIOR_BND_DIAGS * 
 // when the optimiser has its next theta.  seq is stored last (release); ~0: the host has withdrawn the launch.
 struct ThetaBox {
   unsigned long long seq;
-  double s, alpha_scale, v, l, N;
+  double s, alpha_scale, v, l, N, Nw, cw;
   double k[8], dk[8];
   double bnd[2 * PRIOR_BND_DIAGS * PRIOR_BND];
   double dkb[2 * 5 * KI_DKB];
@@ -252,7 +252,9 @@ __device__ __forceinline__ double quad_col(const double* S, long M, long j, cons
   return a;
 }
 
-struct ElboScalars { double v, l, s, N; };
+// N: the rows that count (N+ of a weighted model); Nw = sum of the weights (the -1/2 Nw v/s trace term) and cw = 1/2 D sum log w
+// (asvgp_set_weight_sums).  Unweighted: Nw = N, cw = 0 - the expressions below are then the unweighted ones, bit for bit.
+struct ElboScalars { double v, l, s, N, Nw, cw; };
 
 // The 14 band traces / quadratic forms of the bound and its gradient over `nblk` cooperating workgroups (this one is `bid`);
 // partial sums meet in `gacc` through device-scope atomics, the last workgroup to arrive writes the result and re-arms gacc /
@@ -343,7 +345,7 @@ __device__ __forceinline__ void elbo_finalize_body(
     for (int i = 0; i < NACC; ++i) __hip_atomic_store(gacc + i, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (rearm) __hip_atomic_store(rearm, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double v = th.v, s = th.s, N = th.N, Dd = (double)D;
+    const double v = th.v, s = th.s, N = th.N, Nw = th.Nw, Dd = (double)D;
     // `alpha` may still be the unscaled solve x = P^-1 b (BCR path): alpha = x * alpha_scale; quadratic forms scale^2
     tot[AKA] *= alpha_scale * alpha_scale; tot[ADKA] *= alpha_scale * alpha_scale; tot[AAA] *= alpha_scale * alpha_scale;
     tot[BA] *= alpha_scale;
@@ -358,14 +360,15 @@ __device__ __forceinline__ void elbo_finalize_body(
     elbo += 0.5 * Dd * tot[LOGK];
     elbo -= 0.5 * yy / s;
     elbo += 0.5 * tot[CC];
-    elbo -= 0.5 * N * v / s;
+    elbo -= 0.5 * Nw * v / s;
     elbo += 0.5 * tot[TRKA] / s;
+    if (th.cw != 0.0) elbo += th.cw;
     // G = 1/2 (D Kuu^-1 - D P^-1 - alpha alpha^T - Kuu^-1 A Kuu^-1 / s)   
     double d_l = 0.5 * (Dd * tot[SKDK] - Dd * tot[SPDK] - tot[ADKA] + tot[DTRKA] / s);
-    double d_v = 0.5 * (-Dd * tot[SKK] / v + Dd * tot[SPK] / v + tot[AKA] / v + tot[TRKA] / (v * s)) - 0.5 * N / s;
+    double d_v = 0.5 * (-Dd * tot[SKK] / v + Dd * tot[SPK] / v + tot[AKA] / v + tot[TRKA] / (v * s)) - 0.5 * Nw / s;
     double s2 = s * s;
     double d_s = -0.5 * N * Dd / s + 0.5 * Dd * tot[SPA] / s2 + 0.5 * yy / s2 + 0.5 * tot[AAA] / s2 - tot[BA] / s2 +
-                 0.5 * N * v / s2 - 0.5 * tot[TRKA] / s2;
+                 0.5 * Nw * v / s2 - 0.5 * tot[TRKA] / s2;
     out[0] = elbo; out[1] = d_v; out[2] = d_l; out[3] = d_s;
     out[4] = tot[LOGK]; out[5] = tot[LOGP]; out[6] = tot[TRKA]; out[7] = tot[CC];
   }
@@ -527,7 +530,7 @@ __global__ __launch_bounds__(BM_THREADS) void elbo_chains_mfma_kernel(KuuInterio
     __syncthreads();
     if (gave_up) { if (threadIdx.x == 0) atomicExch(info + 1, -1); return; }
     s_v = box->s; asc_v = box->alpha_scale;
-    th_v.v = box->v; th_v.l = box->l; th_v.s = box->s; th_v.N = box->N;
+    th_v.v = box->v; th_v.l = box->l; th_v.s = box->s; th_v.N = box->N; th_v.Nw = box->Nw; th_v.cw = box->cw;
   }
   const double* stats = fin.stats;
   enum { LOGK, LOGP, TRKA, DTRKA, SKDK, SPDK, SKK, SPK, SPA, CC, AKA, ADKA, AAA, BA, NACC };
@@ -750,7 +753,7 @@ __global__ __launch_bounds__(BM_THREADS) void elbo_chains_mfma_kernel(KuuInterio
 #pragma unroll
   for (int i = 0; i < 14; ++i) __hip_atomic_store(fin.gacc + i, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm (the older kernels ADD into these slots; the message has been read)
   {
-    const double v = th_v.v, sn = th_v.s, N = th_v.N;
+    const double v = th_v.v, sn = th_v.s, N = th_v.N, Nw = th_v.Nw;
     const double yy = stats[(long)(K + 1) * M + M];
     const double asc = asc_v;                                  // x = P^-1 b unscaled: alpha = x / s
     tot[AKA] *= asc * asc; tot[ADKA] *= asc * asc; tot[AAA] *= asc * asc; tot[BA] *= asc;
@@ -764,12 +767,13 @@ __global__ __launch_bounds__(BM_THREADS) void elbo_chains_mfma_kernel(KuuInterio
     elbo += 0.5 * tot[LOGK];
     elbo -= 0.5 * yy / sn;
     elbo += 0.5 * tot[CC];
-    elbo -= 0.5 * N * v / sn;
+    elbo -= 0.5 * Nw * v / sn;
     elbo += 0.5 * tot[TRKA] / sn;
+    if (th_v.cw != 0.0) elbo += th_v.cw;
     const double d_l = 0.5 * (tot[SKDK] - tot[SPDK] - tot[ADKA] + tot[DTRKA] / sn);
-    const double d_v = 0.5 * (-tot[SKK] / v + tot[SPK] / v + tot[AKA] / v + tot[TRKA] / (v * sn)) - 0.5 * N / sn;
+    const double d_v = 0.5 * (-tot[SKK] / v + tot[SPK] / v + tot[AKA] / v + tot[TRKA] / (v * sn)) - 0.5 * Nw / sn;
     const double s2 = sn * sn;
-    const double d_s = -0.5 * N / sn + 0.5 * tot[SPA] / s2 + 0.5 * yy / s2 + 0.5 * tot[AAA] / s2 - tot[BA] / s2 + 0.5 * N * v / s2 - 0.5 * tot[TRKA] / s2;
+    const double d_s = -0.5 * N / sn + 0.5 * tot[SPA] / s2 + 0.5 * yy / s2 + 0.5 * tot[AAA] / s2 - tot[BA] / s2 + 0.5 * Nw * v / s2 - 0.5 * tot[TRKA] / s2;
     double* out = fin.out;
     out[0] = elbo; out[1] = d_v; out[2] = d_l; out[3] = d_s;
     out[4] = tot[LOGK]; out[5] = tot[LOGP]; out[6] = tot[TRKA]; out[7] = tot[CC];
@@ -959,7 +963,7 @@ static int run_chains(Handle* h, const double* stats, const double* S, int kind,
                            tab_k, n_rec, h->node_rec_dev, w.bcrK, w.SK, w.dSK, h->done_dev + slot, seq,
                            gpu_fwd ? dd_ready : (plan_first ? (const unsigned long long*)nullptr : h->ready_dev + slot), spin_limit, ff, box_k);
         if (h->ahead_req) {
-          h->ahead = Handle::PendingAhead{true, slot, seq, tab, kind, (long)ff.th.N};
+          h->ahead = Handle::PendingAhead{true, slot, seq, tab, kind, ff.th.N, ff.th.Nw, ff.th.cw};
           return check_launch("elbo chains (matrix cores, launched ahead of theta)");
         }
         if (gpu_fwd) return check_launch("elbo chains (matrix cores, forward pass on the GPU)");
@@ -1071,7 +1075,9 @@ int ElboLauncher<K>::run(Handle* h, const double* stats, const double* S, int ki
     Ws w = carve(ws, M, K, D);
     bool bcr = false;
     h->mirror_pending = 0;                                    // (set again by the one launch that writes the mirror)
-    ElboScalars th{v, l, s, (double)N};
+    // weighted statistics (asvgp_set_weight_sums): the row count is N+, the trace term takes sum w, the bound gains 1/2 D sum log w
+    ElboScalars th{v, l, s, (double)N, (double)N, 0.0};
+    if (h->w_set) { th.N = h->w_npos; th.Nw = h->w_sum; th.cw = 0.5 * (double)D * h->w_sumlog; }
     const int fin_blocks = (int)((M + 255) / 256 < 64 ? (M + 255) / 256 : 64);
     static_assert(BCR_THREADS == 256, "the fused finalize shares the chain kernel's workgroup size");
     FusedFin ff{stats, th, 1.0 / s, w.fin, reinterpret_cast<unsigned*>(w.fin + 16), reinterpret_cast<unsigned*>(w.fin + 18), nullptr, out, D, 0, 0};
@@ -1325,7 +1331,7 @@ int elbo_publish_theta(Handle* h, double v, double l, double s, bool withdraw) {
       for (int cI = 0; cI < KI_DKB; ++cI)
         bh->dkb[(sd * 5 + d) * KI_DKB + cI] = bnd2[(size_t)(sd * PRIOR_BND_DIAGS + d) * PRIOR_BND + cI];
   for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) bh->dc[t] = cf.dc[t];
-  bh->s = s; bh->alpha_scale = 1.0 / s; bh->v = v; bh->l = l; bh->N = (double)a.N;
+  bh->s = s; bh->alpha_scale = 1.0 / s; bh->v = v; bh->l = l; bh->N = a.N; bh->Nw = a.Nw; bh->cw = a.cw;
   __atomic_store_n(&bh->seq, a.seq, __ATOMIC_RELEASE);          // the kernel proceeds: P chain at once, the Kuu workgroup waits for the table
   if (h->defer_forward) {                                       // (asvgp_set_deferred_forward_pass(h, 1): the caller enqueues other work first, then asvgp_prior_publish)
     h->fwd.valid = true;

@@ -271,6 +271,18 @@ extern "C" int asvgp_set_phi_workgroups(asvgp_handle_t handle, int n) {
   return ASVGP_OK;
 }
 
+// The three scalars of per-observation weights that the bound needs beside the weighted statistics (asvgp_hip.h).  n_pos < 0: unweighted.
+extern "C" int asvgp_set_weight_sums(asvgp_handle_t handle, double n_pos, double sum_w, double sum_log_w) {
+  Handle* h = as_handle(handle);
+  if (n_pos < 0.0) { h->w_set = false; h->w_npos = h->w_sum = h->w_sumlog = 0.0; return ASVGP_OK; }
+  if (!(n_pos == n_pos) || n_pos != (double)(long long)n_pos || n_pos > 9.0e15 || !(sum_w >= 0.0) || !(sum_w < 1e300) || !(fabs(sum_log_w) < 1e300)) {
+    set_error("set_weight_sums: n_pos must be a whole number of rows (negative: unweighted), sum_w >= 0 and sum_log_w finite");
+    return ASVGP_ERR_BAD_ARG;
+  }
+  h->w_set = true; h->w_npos = n_pos; h->w_sum = sum_w; h->w_sumlog = sum_log_w;
+  return ASVGP_OK;
+}
+
 extern "C" int asvgp_set_phi_deferred_reduce(asvgp_handle_t handle, int on) {
   Handle* h = as_handle(handle);
   h->phi_defer = on != 0;

@@ -15,7 +15,7 @@ struct Handle {
   int device = 0;
   // Phi pass
   int phi_algo = 0, phi_blocks = 0;
-  int phi_last = 0;                       // algorithm the last asvgp_phi_accumulate_1d actually ran (1, 3, 5, 6)
+  int phi_last = 0;                       // algorithm the last asvgp_phi_accumulate_1d[_weighted] actually ran (1, 3, 5, 6; weighted: 11 band scatter, 16 register moments)
   // deferred cross-workgroup reduce (asvgp_set_phi_deferred_reduce): the moment kernel's partials wait here for asvgp_phi_reduce_1d
   bool phi_defer = false;
   struct PendingReduce { const double* partials; int G, M, K; double* stats; bool valid; const int* ranges; } pend = {nullptr, 0, 0, 0, nullptr, false, nullptr};
@@ -81,7 +81,11 @@ struct Handle {
   bool ahead_req = false;                 // set by the entry point around its call into the launcher
   void* box_host = nullptr;               // TAB_SLOTS x BOX_BYTES, pinned + mapped
   void* box_dev = nullptr;
-  struct PendingAhead { bool valid; int slot; unsigned long long seq; double* tab; int kind; long N; } ahead = {false, 0, 0, nullptr, 0, 0};
+  struct PendingAhead { bool valid; int slot; unsigned long long seq; double* tab; int kind; double N, Nw, cw; } ahead = {false, 0, 0, nullptr, 0, 0.0, 0.0, 0.0};
+  // per-observation weights (asvgp_set_weight_sums): the three scalars of the weights the bound needs beside the weighted statistics.
+  // w_set = false: unweighted (the N argument of the ELBO entries counts, as always).
+  bool w_set = false;
+  double w_npos = 0.0, w_sum = 0.0, w_sumlog = 0.0;
 };
 constexpr size_t BOX_BYTES = 4096;
 

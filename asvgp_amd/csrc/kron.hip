@@ -1918,3 +1918,5 @@ extern "C" int asvgp_phi_accumulate_kron2d_sorted_f32(const float* Xs, const flo
                                                       double* stats, asvgp_stream_t stream) {
   return phi_accumulate_kron2d_sorted_entry<float>(Xs, ys, N, cell_start, mesh1, n_mesh1, delta1, m1, mesh2, n_mesh2, delta2, m2, order, stats, stream);
 }
+
+#include "kron_weighted.hpp"

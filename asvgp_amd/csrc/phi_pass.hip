@@ -1158,3 +1158,5 @@ extern "C" int asvgp_predict_deriv_1d(asvgp_handle_t handle, const double* xnew,
     default: return launch_predict<6, 1>(nullptr, xnew, n, mesh, (int)n_mesh, delta, (int)M, alpha, W, prior, (int)D, mean, var, st);
   }
 }
+
+#include "phi_weighted.hpp"

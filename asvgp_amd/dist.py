@@ -15,12 +15,21 @@ def shard_bounds(N, world_size, rank):
     return lo, hi
 
 
-def allreduce_stats(stats, n_local, group=None):
+def allreduce_stats(stats, n_local, group=None, wstats=None):
     """Sum the packed statistics buffer and the local row count across ranks.  Returns global N (python int).
-    One collective for the payload (98 312 B at M=2048, k=4); the count rides in a second 8-byte all-reduce."""
-    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return int(n_local)
-    dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
-    n = torch.tensor([float(n_local)], dtype=torch.float64, device=stats.device)
-    dist.all_reduce(n, op=dist.ReduceOp.SUM, group=group)
-    return int(round(n.item()))
+    One collective for the payload (98 312 B at M=2048, k=4); the count rides in a second 8-byte all-reduce.
+    wstats (weighted models): this rank's [sum w, sum log w, N+] (3 doubles, device or host) rides with the count - the second
+    collective is then 32 bytes, the payload collective is unchanged - and (N, [the three global sums]) is returned."""
+    scalars = [float(n_local)]                 # what the second collective carries: the count, then the three weight sums
+    if wstats is not None:
+        w = torch.as_tensor(wstats, dtype=torch.float64).reshape(-1)
+        if w.numel() != 3:
+            raise ValueError("allreduce_stats: wstats must hold [sum w, sum log w, N+]")
+        scalars += w.tolist()
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
+        n = torch.tensor(scalars, dtype=torch.float64, device=stats.device)
+        dist.all_reduce(n, op=dist.ReduceOp.SUM, group=group)
+        scalars = n.tolist()
+    n_global = int(round(scalars[0]))
+    return n_global if wstats is None else (n_global, scalars[1:])

@@ -41,6 +41,31 @@ def _require_inside(col, a, b, strict, what):
                              % (what, "strictly inside" if strict else "inside", a, b, lo, hi))
 
 
+def _prepare_weights(weights, n, dev, what):
+    """Per-observation weights (noise variance sigma2 / w_i): array-like (N,) or (N, 1) -> fp64 device tensor (N,), validated once
+    like _require_inside: every weight finite and >= 0, else ValueError naming the first bad row."""
+    w = _to_device(weights, dev)
+    if w.dim() == 2 and w.shape[1] == 1:
+        w = w.reshape(-1)
+    if w.dim() != 1 or w.shape[0] != n:
+        raise ValueError("%s: weights must have shape (N,) or (N, 1) with N = %d rows; got %s" % (what, n, tuple(torch.as_tensor(weights).shape)))
+    bad = ~(torch.isfinite(w) & (w >= 0))
+    if w.numel() and bool(bad.any()):
+        i = int(torch.nonzero(bad)[0].item())
+        raise ValueError("%s: weights must be finite and >= 0; row %d has weight %r" % (what, i, w[i].item()))
+    return w.contiguous()
+
+
+def _predictive_weights(weights, n):
+    """weights of predict_y / predict_log_density for the NEW points: (n, 1) numpy column, every entry finite and > 0."""
+    w = np.asarray(weights.cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64).reshape(-1, 1)
+    if w.shape[0] != n:
+        raise ValueError("weights must have one entry per new point (%d); got %d" % (n, w.shape[0]))
+    if not np.all(np.isfinite(w) & (w > 0)):
+        raise ValueError("weights of new points must be finite and > 0 (noise variance sigma2 / w)")
+    return w
+
+
 class _ShardedStats:
     """N-sharded statistics: every (re)run of the local Phi pass is followed by the ONE all-reduce of the
     packed buffer, so `_stats` (and the views KufKfu / Kuf_y / tr_yTy into it) are always the global sums."""
@@ -96,15 +121,34 @@ class _GPModelSurface:
     def trainable_variables(self):
         return self.trainable_parameters
 
-    def predict_y(self, Xnew):
-        mean, var = self.predict_f(Xnew)
-        return _host(mean), _host(var + float(self.likelihood.variance))
+    # per-observation weights (None: the unweighted model)
+    weights = None
+    weight_sum = None
+    log_weight_sum = None
 
-    def predict_log_density(self, data):
+    def _set_weight_sums(self, n_local, wstats_local, process_group):
+        """Global [N+, sum w, sum log w] of a weighted model from this rank's wstats = [sum w, sum log w, N+] (device, 3 doubles); the
+        payload collective of a sharded model is the usual one, the three scalars ride with the row count."""
+        if self._distributed:
+            _, ws = allreduce_stats(self._stats, n_local, process_group, wstats=wstats_local)
+        else:
+            ws = wstats_local.tolist()
+        self.weight_sum, self.log_weight_sum, self.num_data = float(ws[0]), float(ws[1]), int(round(ws[2]))
+
+    def predict_y(self, Xnew, weights=None):
+        """Mean and variance of a new observation; weights: per-point w of the NEW points (noise variance sigma2 / w; default 1)."""
+        mean, var = self.predict_f(Xnew)
+        noise = float(self.likelihood.variance)
+        if weights is not None:
+            noise = noise / _predictive_weights(weights, np.asarray(var).shape[0])
+        return _host(mean), _host(var + noise)
+
+    def predict_log_density(self, data, weights=None):
         """gpflow GPModel.predict_log_density with the Gaussian likelihood: log N(y | mean, var_f + sigma2) summed over the output
-        dimension - shape (N,) (gpflow/likelihoods/scalar_continuous.py Gaussian._predict_log_density: reduce_sum over the last axis)."""
+        dimension - shape (N,) (gpflow/likelihoods/scalar_continuous.py Gaussian._predict_log_density: reduce_sum over the last axis).
+        weights: as predict_y."""
         Xnew, Ynew = data
-        mean, var = self.predict_y(Xnew)
+        mean, var = self.predict_y(Xnew, weights)
         Ynew = np.asarray(Ynew.cpu() if isinstance(Ynew, torch.Tensor) else Ynew, dtype=np.float64).reshape(mean.shape)
         return _host(np.sum(-0.5 * (np.log(2 * np.pi * var) + (Ynew - mean) ** 2 / var), axis=-1))
 
@@ -125,7 +169,7 @@ class _GPModelSurface:
 
 
 class GPR_1d(_GPModelSurface, _ShardedStats):
-    def __init__(self, data, kernel, basis, process_group=None, distributed=None):
+    def __init__(self, data, kernel, basis, process_group=None, distributed=None, *, weights=None):
         # Check inputs (gpr.py:22-26)
         assert isinstance(kernel, (kernels.Matern12, kernels.Matern32, kernels.Matern52))
         assert data[0].shape[1] == 1
@@ -135,6 +179,8 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
             self.y = self.y.reshape(-1, 1)
         require_cuda(self.X, self.y)
         _require_inside(self.X, basis.a, basis.b, True, "GPR_1d")
+        if weights is not None:               # observation i has noise variance sigma2 / w_i; w_i = 0: the row is absent
+            self.weights = _prepare_weights(weights, self.X.shape[0], dev, "GPR_1d")
         # Init model (gpr.py:29-34)
         self.kernel = kernel
         self.likelihood = kernels.Gaussian()
@@ -149,13 +195,19 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._h = Handle()                    # library state of THIS model (asvgp_create)
         self._planned_kind = None
         self._stats = torch.empty((k + 1) * M + M * D + 1, dtype=torch.float64, device=dev)
-        wsb = lib.asvgp_phi_workspace_bytes(M, k, D)
+        wsb = lib.asvgp_phi_workspace_bytes(M, k, D) if self.weights is None else lib.asvgp_phi_weighted_workspace_bytes(M, k, D)
         self._phi_ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
         self._wsb = wsb
         self._setup_dist(process_group, distributed)
+        if self.weights is not None:
+            self._wstats = torch.zeros(3, dtype=torch.float64, device=dev)
         self._phi_pass_local()
-        self.num_data = allreduce_stats(self._stats, self.num_data_local, process_group) if self._distributed \
-            else self.num_data_local
+        if self.weights is None:
+            self.num_data = allreduce_stats(self._stats, self.num_data_local, process_group) if self._distributed \
+                else self.num_data_local
+        else:                                 # N+ rows count; the fused ELBO launch takes the three scalars from the handle
+            self._set_weight_sums(self.num_data_local, self._wstats, process_group)
+            self._h.set_weight_sums(self.num_data, self.weight_sum, self.log_weight_sum)
         self.KufKfu = self._stats[:(k + 1) * M].view(k + 1, M)
         self.Kuf_y = self._stats[(k + 1) * M:(k + 1) * M + M * D].view(M, D)
         self.tr_yTy = self._stats[-1]
@@ -173,6 +225,12 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
     def _phi_pass_local(self):
         """asvgp_phi_accumulate_1d over this rank's rows -> packed [band | Phi y | y^T y] (local sums)."""
         b = self.basis
+        if self.weights is not None:
+            check(get_lib().asvgp_phi_accumulate_1d_weighted(self._h.ptr, self.X.data_ptr(), self.y.data_ptr(), self.weights.data_ptr(),
+                                                             self.X.shape[0], self.D, b.mesh.data_ptr(), b.mesh.shape[0], b.delta_np,
+                                                             b.order, b.m, self._stats.data_ptr(), self._wstats.data_ptr(),
+                                                             self._phi_ws.data_ptr(), self._wsb, stream_ptr()), "phi_accumulate_1d_weighted")
+            return self._stats
         check(get_lib().asvgp_phi_accumulate_1d(self._h.ptr, self.X.data_ptr(), self.y.data_ptr(), self.X.shape[0], self.D,
                                                 b.mesh.data_ptr(), b.mesh.shape[0], b.delta_np, b.order, b.m,
                                                 self._stats.data_ptr(), self._phi_ws.data_ptr(), self._wsb,
@@ -570,8 +628,11 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
     blocked band Cholesky - the reference runs dense O(M_tot^3) tf.linalg.cholesky (gpr.py:293).  That is the d = 2 path (every
     reference configuration); any other d takes the reference's own dense route on the device (_init_dense), small grids only."""
 
-    def __init__(self, data, kernels, bases, process_group=None, distributed=None):
+    def __init__(self, data, kernels, bases, process_group=None, distributed=None, *, weights=None):
         dev = bases[0].device
+        if weights is not None and len(bases) != 2:
+            raise NotImplementedError("GPR_kron(weights=...) is implemented for d = 2 (the block-band route) only: the dense and n-d band "
+                                      "routes of d = %d have no weighted Phi pass yet" % len(bases))
         # fp32 data (BASELINE configs[3]): the cell-sorted copy the Phi pass streams stays fp32 (12 B per point); X / y themselves are
         # widened once, as the reference does (basis.py:54) - the widening is exact, so the statistics are those of the fp64 data
         self._fp32_storage = (torch.as_tensor(data[0]).dtype == torch.float32 and torch.as_tensor(data[1]).dtype == torch.float32)
@@ -579,6 +640,9 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         require_cuda(self.X, self.y)                         # (both routes below hand raw device pointers to the library)
         self.n, self.d = self.X.shape[0], self.X.shape[1]
         assert len(kernels) == len(bases) == self.d          # gpr.py:247
+        if weights is not None:                              # observation i has noise variance sigma2 / w_i; w_i = 0: the row is absent
+            self.weights = _prepare_weights(weights, self.n, dev, "GPR_kron")
+            self._fp32_storage = False                       # (no weighted fp32-storage kernel: weighted fp32 data stream as fp64)
         assert self.y.shape[1] == 1                          # gpr.py:248
         for kern in kernels:
             assert isinstance(kern, (kernels_mod.Matern12, kernels_mod.Matern32, kernels_mod.Matern52))
@@ -602,8 +666,13 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         self.noff = k * (2 * k + 1) + k + 1
         self._stats = torch.empty(lib.asvgp_kron_stats_doubles(m1, m2, k), dtype=torch.float64, device=dev)
         self._setup_dist(process_group, distributed)
+        if self.weights is not None:
+            self._wstats = torch.zeros(3, dtype=torch.float64, device=dev)
         self._phi_pass_local()
-        self.num_data = allreduce_stats(self._stats, self.n, process_group) if self._distributed else self.n
+        if self.weights is None:
+            self.num_data = allreduce_stats(self._stats, self.n, process_group) if self._distributed else self.n
+        else:
+            self._set_weight_sums(self.n, self._wstats, process_group)
         self.KufKfu_blockband = self._stats[:self.noff * self.Mtot].view(self.noff, self.Mtot)
         self.Kuf_y = self._stats[self.noff * self.Mtot:self.noff * self.Mtot + self.Mtot].view(self.Mtot, 1)
         self.tr_yTy = self._stats[-1]
@@ -899,6 +968,8 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         start = torch.zeros(ncell + 1, dtype=torch.int64, device=dev)
         start[1:] = torch.cumsum(counts, 0)
         Xs, ys = self.X[order].contiguous(), self.y[order].contiguous()
+        if self.weights is not None:
+            return Xs, ys, start, self.weights[order].contiguous()
         if getattr(self, "_fp32_storage", False):
             Xs, ys = Xs.to(torch.float32), ys.to(torch.float32)   # (exact: the data WERE fp32)
         return Xs, ys, start
@@ -910,6 +981,22 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
             return self._dense_phi_pass()
         b1, b2 = self.bases
         lib = get_lib()
+        if self.weights is not None:
+            if sorted_cells and self.n > 0:
+                if getattr(self, "_sorted", None) is None:
+                    self._sorted = self._sort_by_cell()
+                Xs, ys, start, ws = self._sorted
+                check(lib.asvgp_phi_accumulate_kron2d_sorted_weighted(Xs.data_ptr(), ys.data_ptr(), ws.data_ptr(), self.n, start.data_ptr(),
+                                                                      b1.mesh.data_ptr(), b1.mesh.shape[0], b1.delta_np, b1.m,
+                                                                      b2.mesh.data_ptr(), b2.mesh.shape[0], b2.delta_np, b2.m, self.order,
+                                                                      self._stats.data_ptr(), self._wstats.data_ptr(), stream_ptr()),
+                      "phi_accumulate_kron2d_sorted_weighted")
+            else:
+                check(lib.asvgp_phi_accumulate_kron2d_weighted(self.X.data_ptr(), self.y.data_ptr(), self.weights.data_ptr(), self.n,
+                                                               b1.mesh.data_ptr(), b1.mesh.shape[0], b1.delta_np, b1.m, b2.mesh.data_ptr(),
+                                                               b2.mesh.shape[0], b2.delta_np, b2.m, self.order, self._stats.data_ptr(),
+                                                               self._wstats.data_ptr(), stream_ptr()), "phi_accumulate_kron2d_weighted")
+            return self._stats
         if sorted_cells and self.n > 0:
             if getattr(self, "_sorted", None) is None:
                 self._sorted = self._sort_by_cell()
@@ -1097,14 +1184,24 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
             return self._dense_elbo_and_grad(want_grad=False)[0]
         f = self._factor(want_alpha=False)
         s = f["s"]
-        N = float(self.num_data)
+        N, Nw, cw = self._bound_scalars()
         vprod = 1.0
         for kern in self.kernels:
             vprod *= float(kern.variance)                    # gpr.py:284: prod of K_diag
         elbo = -0.5 * N * math.log(2 * math.pi * s)
         elbo = elbo - 0.5 * f["logdet_P"] + 0.5 * f["logdet_K"] - 0.5 * self.tr_yTy / s
-        elbo = elbo + 0.5 * f["cc"] - 0.5 * N * vprod / s + 0.5 * f["trace"] / s
+        elbo = elbo + 0.5 * f["cc"] - 0.5 * Nw * vprod / s + 0.5 * f["trace"] / s
+        if cw:
+            elbo = elbo + cw
         return elbo
+
+    def _bound_scalars(self):
+        """(N, Nw, cw) of the bound: the -1/2 N log 2 pi s term counts the rows (N+ of a weighted model), the -1/2 Nw v / s trace term
+        takes the sum of the weights, cw = 1/2 sum log w is added.  Unweighted: (N, N, 0) - the expressions are the unweighted ones."""
+        N = float(self.num_data)
+        if self.weights is None:
+            return N, N, 0.0
+        return N, self.weight_sum, 0.5 * self.log_weight_sum
 
     def maximum_log_likelihood_objective(self):
         return self.elbo()
@@ -1228,7 +1325,8 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
             return float(e), g.cpu().numpy()
         f = self._factor(want_alpha=False)
         SigD, SigS, Bb = self._selinv(f)                         # (also fills f["alpha"])
-        s, N = f["s"], float(self.num_data)
+        s = f["s"]
+        N, Nw, cw = self._bound_scalars()
         vs = [float(k.variance) for k in self.kernels]
         ls = [float(k.lengthscales) for k in self.kernels]
         dKs = f["dKs"]
@@ -1242,13 +1340,15 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         yy = float(self.tr_yTy)
         vprod = vs[0] * vs[1]
         elbo = (-0.5 * N * math.log(2 * math.pi * s) - 0.5 * float(f["logdet_P"]) + 0.5 * float(f["logdet_K"]) - 0.5 * yy / s
-                + 0.5 * cc - 0.5 * N * vprod / s + 0.5 * tSA / s)
+                + 0.5 * cc - 0.5 * Nw * vprod / s + 0.5 * tSA / s)
+        if cw:
+            elbo = elbo + cw
         mo = [b2.m, b1.m]                                        # size of the OTHER factor: tr((K1^-1 dK1) (x) I_m2) = m2 tr(K1^-1 dK1)
         g = np.zeros(5)
         for i, (tPX, aXa, tZA) in enumerate(((tPX1, aX1a, tZ1A), (tPX2, aX2a, tZ2A))):
             g[2 * i + 1] = -0.5 * tPX + 0.5 * mo[i] * trK[i] - 0.5 * aXa - 0.5 * tZA / s            # d / d l_i
-            g[2 * i] = (0.5 * tPK - 0.5 * self.Mtot + 0.5 * aKa + 0.5 * tSA / s) / vs[i] - 0.5 * N * vprod / (vs[i] * s)   # d / d v_i  (dKuu = -Kuu / v_i)
-        g[4] = (-0.5 * N / s + 0.5 * tPA / s ** 2 - cc / s + 0.5 * aAa / s ** 2 + 0.5 * yy / s ** 2 + 0.5 * N * vprod / s ** 2
+            g[2 * i] = (0.5 * tPK - 0.5 * self.Mtot + 0.5 * aKa + 0.5 * tSA / s) / vs[i] - 0.5 * Nw * vprod / (vs[i] * s)   # d / d v_i  (dKuu = -Kuu / v_i)
+        g[4] = (-0.5 * N / s + 0.5 * tPA / s ** 2 - cc / s + 0.5 * aAa / s ** 2 + 0.5 * yy / s ** 2 + 0.5 * Nw * vprod / s ** 2
                 - 0.5 * tSA / s ** 2)
         return elbo, g
 
@@ -1449,7 +1549,10 @@ class GPR_additive(_GPModelSurface, _ShardedStats):
     (Cholesky of P = blockdiag(Kuu_i) + KufKfu / sigma2, gpr.py:191-194) stays dense as in the reference (rocSOLVER through
     torch.linalg); log|Kuu| and tr(Kuu^-1 KufKfu) use the banded operators block by block."""
 
-    def __init__(self, data, kernels, bases, process_group=None, distributed=None):
+    def __init__(self, data, kernels, bases, process_group=None, distributed=None, *, weights=None):
+        if weights is not None:
+            raise NotImplementedError("GPR_additive(weights=...): per-observation weights are implemented for GPR_1d and GPR_kron (d = 2) "
+                                      "only - the additive model's cross blocks have no weighted Phi pass yet")
         dev = bases[0].device
         self.X, self.y = _to_device(data[0], dev), _to_device(data[1], dev)
         self.n, self.d = self.X.shape[0], self.X.shape[1]

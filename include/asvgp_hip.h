@@ -130,7 +130,8 @@ int asvgp_elbo_grad_host_1d(asvgp_handle_t handle, const double* stats, const do
                             double lengthscale, double noise_variance, int64_t N, int64_t M, int k, int64_t D,
                             double* out, int* info, void* workspace, size_t workspace_bytes, asvgp_stream_t stream,
                             double* result10, double timeout_seconds);
-/* the algorithm the handle's last asvgp_phi_accumulate_1d call actually ran (1, 3, 5 or 6; 0 before the first call) */
+/* the algorithm the handle's last asvgp_phi_accumulate_1d call actually ran (1, 3, 5 or 6; 0 before the first call);
+ * after asvgp_phi_accumulate_1d_weighted: 11 (weighted fp64 band scatter) or 16 (weighted register moments), see that entry */
 int asvgp_phi_last_algorithm(asvgp_handle_t handle);
 /* Input order of the tile-sort Phi pass.  A time series (sorted / locally sorted x - the order of the reference's own large 1-D data,
  * experiments/large_regression/electricity.py:31-32) needs no sort: the instantiation with the time-series front loop sums such
@@ -154,6 +155,47 @@ int asvgp_set_phi_workgroups(asvgp_handle_t handle, int n);
  * caller thereby keeps its N-side stream to the streaming kernels alone.  asvgp_phi_reduce_1d without a pending reduce is a no-op. */
 int asvgp_set_phi_deferred_reduce(asvgp_handle_t handle, int on);
 int asvgp_phi_reduce_1d(asvgp_handle_t handle, asvgp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-observation noise weights.  Observation i carries noise variance sigma2 / w_i (w_i >= 0 fixed and finite, sigma2 still the
+ * trainable scale).  A row with w_i = 0 is ABSENT: it contributes to nothing, the row count included.  With
+ *   N+ = #{w_i > 0},  Sw = sum w_i,  L = sum_{w_i > 0} log w_i,
+ *   A_w = Phi W Phi^T,  b_w = Phi W y,  yy_w = sum w_i y_i^2
+ * and bound(A, b, yy, N) the collapsed bound as asvgp_elbo_grad_1d evaluates it from statistics (for D > 1 it counts the two trace
+ * terms once, as the reference does), v the kernel variance (product of the factors' variances for the Kronecker model):
+ *   ELBO_w          = bound(A_w, b_w, yy_w, N+) + 1/2 D L - 1/2 (Sw - N+) v / sigma2
+ *   dELBO_w/dv      = dbound/dv      - 1/2 (Sw - N+) / sigma2
+ *   dELBO_w/dsigma2 = dbound/dsigma2 + 1/2 (Sw - N+) v / sigma2^2,      dELBO_w/dl = dbound/dl
+ * i.e. the -1/2 N log(2 pi sigma2) term keeps N+ and the -1/2 N v / sigma2 term takes Sw.  This equals
+ * log N(y | 0, Qff + diag(sigma2 / w)) - 1/2 sum w_i (v - q_ii) / sigma2 over the rows with w_i > 0.  The posterior of f is the
+ * usual algebra on (A_w, b_w): every consumer of `stats` serves a weighted model as it is.  w = 1 everywhere is the unweighted model.
+ *
+ * asvgp_phi_accumulate_1d_weighted: asvgp_phi_accumulate_1d with w (N doubles).  stats: the same packed layout holding A_w, b_w, yy_w;
+ * wstats (device, 3 doubles, overwritten) = [Sw, L, N+].  It accepts whatever the unweighted entry accepts (orders 1..6, any M, D >= 1 -
+ * one weight vector shared by all outputs -, float32-linspace meshes, any alignment and input order, N = 0).  Workspace:
+ * asvgp_phi_weighted_workspace_bytes (never less than asvgp_phi_workspace_bytes, whose values are unchanged).
+ *   Two kernels; asvgp_phi_last_algorithm reports which one the last call ran:
+ *     16 = weighted register moments (the design of algorithm 6: points counting-sorted by cell inside the LDS, per-cell sums
+ *          S_p = sum w s^p - S_0 a floating sum - and T_p = sum w y s^p in the registers of the thread that owns the cell).  It applies
+ *          when D = 1, N >= 2, M <= 2048, x / y / w are 16-byte aligned and the mesh is an exact numpy.linspace;
+ *     11 = weighted fp64 band scatter (the design of algorithm 1 with a weight): everything the entry accepts.
+ *   asvgp_set_phi_algorithm with weights: 0 = auto: 16 where it applies, else 11;  1 = always 11;  6 = 16, or ASVGP_ERR_UNSUPPORTED
+ *   with a message where 16 does not apply;  3 and 5 are refused with ASVGP_ERR_UNSUPPORTED: fixed-point scales are bounds on the
+ *   unweighted products, which w breaks.  Both kernels return the same statistics to <= 1e-12 of each block's largest entry.
+ *   Invalid weights (negative, NaN, +-inf) are reported the way a point outside the mesh is: yy_w = NaN (the models check first).
+ *   A row with w = 0 may hold any finite x inside the mesh and any finite y.
+ *   asvgp_set_phi_workgroups is honoured.  asvgp_set_phi_deferred_reduce has no effect on this entry: it always enqueues its own
+ *   reduce (after a reduce still parked on the handle), so a later asvgp_phi_reduce_1d is the documented no-op.
+ *
+ * asvgp_set_weight_sums: the three scalars for the handle's ELBO launches - asvgp_elbo_grad_1d, asvgp_elbo_grad_host_1d,
+ * asvgp_elbo_grad_ahead_1d (captured at the ahead call) + asvgp_elbo_publish_theta, asvgp_elbo_data_chain_1d and the result mirror then
+ * return ELBO_w and its gradient when `stats` holds weighted statistics; their N argument is superseded by n_pos.  n_pos < 0 returns the
+ * handle to the unweighted bound (the default), whose arithmetic is unchanged to the bit. */
+size_t asvgp_phi_weighted_workspace_bytes(int64_t M, int order, int64_t D);
+int asvgp_phi_accumulate_1d_weighted(asvgp_handle_t handle, const double* x, const double* y, const double* w, int64_t N, int64_t D,
+                                     const double* mesh, int64_t n_mesh, double delta, int order, int64_t M, double* stats,
+                                     double* wstats, void* workspace, size_t workspace_bytes, asvgp_stream_t stream);
+int asvgp_set_weight_sums(asvgp_handle_t handle, double n_pos, double sum_w, double sum_log_w);
 
 /* basis.py:58-59  neighbour_index = relu(searchsorted_left(mesh, x) - 1)  (integer work, bit-exact) */
 int asvgp_phi_index_1d(const double* x, int64_t N, const double* mesh, int64_t n_mesh, double delta,
@@ -421,6 +463,19 @@ int asvgp_phi_accumulate_kron2d_sorted_f32(const float* Xs, const float* ys, int
                                            const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
                                            const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
                                            double* stats, asvgp_stream_t stream);
+/* The weighted forms (see "Per-observation noise weights" above): w / ws = N weights in the order of the points; the same `stats`
+ * layout holding Phi W Phi^T, Phi W y, sum w y^2; wstats (device, 3 doubles, overwritten) = [sum w, sum_{w>0} log w, #{w > 0}].
+ * Per point: every product scaled by w, rows with w = 0 skipped.  Cell-sorted: a cell's share Phi_c^T diag(w) Phi_c on the matrix
+ * core (one operand of the v_mfma_f64_16x16x4 products scaled by w) + the gather of the unweighted entry; it needs the staging buffer
+ * (ASVGP_ERR_HIP when there is no room - the per-point entry needs none).  The fp32-storage entry has no weighted twin: weighted fp32
+ * data take the fp64 cell-sorted path.  Invalid weights (negative, NaN, +-inf): sum w y^2 = NaN. */
+int asvgp_phi_accumulate_kron2d_weighted(const double* X, const double* y, const double* w, int64_t N, const double* mesh1, int64_t n_mesh1,
+                                         double delta1, int64_t m1, const double* mesh2, int64_t n_mesh2, double delta2,
+                                         int64_t m2, int order, double* stats, double* wstats, asvgp_stream_t stream);
+int asvgp_phi_accumulate_kron2d_sorted_weighted(const double* Xs, const double* ys, const double* ws, int64_t N, const int64_t* cell_start,
+                                                const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
+                                                const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
+                                                double* stats, double* wstats, asvgp_stream_t stream);
 
 /* Selected inverse of P = Kuu + KufKfu/sigma2 on the band (what the gradient of gpr.py:282-308 and the predictive variance
  * of gpr.py:319-330 need of P^-1), through dense super-blocks of size Bb (a multiple of 32, >= bw): the band factor is
