@@ -74,6 +74,9 @@ SIGNATURES = {
     "asvgp_elbo_prior_chain_1d": (_I, [_P, _P, _I, _D, _D, _D, _L, _I, _L, _P, _P, _Z, _P]),
     "asvgp_elbo_data_chain_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _L, _I, _L, _P, _P, _P, _Z, _P]),
     "asvgp_posterior_prepare_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _I, _L, _P, _P, _P, _P, _Z, _P]),
+    "asvgp_posterior_prepare_loo_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _I, _L, _P, _P, _P, _P, _P, _Z, _P]),
+    "asvgp_loo_workspace_bytes": (_Z, [_L, _I, _L]),
+    "asvgp_loo_1d": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_predict_1d": (_I, [_P, _L, _P, _L, _D, _I, _L, _P, _P, _D, _L, _P, _P, _P]),
     "asvgp_predict_1d_h": (_I, [_P, _P, _L, _P, _L, _D, _I, _L, _P, _P, _D, _L, _P, _P, _P]),
     "asvgp_posterior_cov_workspace_bytes": (_Z, [_L, _I, _L]),

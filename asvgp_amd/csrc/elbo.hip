@@ -72,9 +72,9 @@ template <int K> struct KuuInvLauncher {   // band(Kuu^-1) and its d/d-lengthsca
   static int run(Handle* h, const double* S, int kind, double v, double l, long M, double* Kuu, double* dK, double* SK, double* dSK,
                  double* logdet2, int* info, void* ws, hipStream_t st);
 };
-template <int K> struct PostLauncher {
+template <int K> struct PostLauncher {   // Pinv != NULL (asvgp_posterior_prepare_loo_1d): band(P^-1) as the P chain leaves it, copied out as well
   static int run(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
-                 double* alpha, double* W, int* info, void* ws, hipStream_t st);
+                 double* alpha, double* W, int* info, void* ws, hipStream_t st, double* Pinv = nullptr);
 };
 // the posterior chain, then the whole of P^-1 - Kuu^-1 (asvgp_posterior_cov_prepare_1d).  Its scratch follows the ELBO workspace:
 // Kuu, P, L_K, L_P bands, the two reciprocal diagonals and two info slots of the plain band Cholesky factorisations.
@@ -1093,7 +1093,7 @@ int ElboLauncher<K>::run(Handle* h, const double* stats, const double* S, int ki
 }
 template <int K>
 int PostLauncher<K>::run(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
-                         double* alpha, double* W, int* info, void* ws, hipStream_t st) {
+                         double* alpha, double* W, int* info, void* ws, hipStream_t st, double* Pinv) {
   {
     Ws w = carve(ws, M, K, D);
     bool bcr = false;
@@ -1102,8 +1102,9 @@ int PostLauncher<K>::run(Handle* h, const double* stats, const double* S, int ki
     long E = (long)(K + 1) * M;
     hipLaunchKernelGGL(scale_sub_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, w.SP, w.SK, W, E);
     hipError_t e = hipMemcpyAsync(alpha, w.alpha, sizeof(double) * M * D, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && Pinv) e = hipMemcpyAsync(Pinv, w.SP, sizeof(double) * E, hipMemcpyDeviceToDevice, st);   // the chain's own band(P^-1), not W + band(Kuu^-1)
     if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return ASVGP_ERR_HIP; }
-    return check_launch("posterior_prepare_1d");
+    return check_launch(Pinv ? "posterior_prepare_loo_1d" : "posterior_prepare_1d");
   }
 }
 
@@ -1512,6 +1513,24 @@ extern "C" int asvgp_posterior_prepare_1d(asvgp_handle_t handle, const double* s
   { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }   // (a deferred Phi reduce into THIS buffer goes first)
   hipStream_t st = as_stream(stream);
 #define POST_CASE(KK) case KK: return PostLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st);
+  switch (k) { POST_CASE(1) POST_CASE(2) POST_CASE(3) POST_CASE(4) POST_CASE(5) POST_CASE(6) }
+#undef POST_CASE
+  return ASVGP_ERR_UNSUPPORTED;
+}
+
+// asvgp_posterior_prepare_1d with band(P^-1) as a third output (the leave-one-out leverages of asvgp_loo_1d need P^-1 itself)
+extern "C" int asvgp_posterior_prepare_loo_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
+                                              double lengthscale, double noise_variance, int64_t M, int k, int64_t D,
+                                              double* alpha, double* W, double* Pinv_band, int* info, void* workspace, size_t workspace_bytes,
+                                              asvgp_stream_t stream) {
+  int rc = elbo_args_ok(stats, static_bands, alpha, M, k, D, variance, lengthscale, noise_variance, workspace,
+                        workspace_bytes, info, "posterior_prepare_loo_1d");
+  if (rc) return rc;
+  if (!W || !Pinv_band) { set_error("posterior_prepare_loo_1d: bad argument"); return ASVGP_ERR_BAD_ARG; }
+  Handle* h = as_handle(handle);
+  { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }
+  hipStream_t st = as_stream(stream);
+#define POST_CASE(KK) case KK: return PostLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st, Pinv_band);
   switch (k) { POST_CASE(1) POST_CASE(2) POST_CASE(3) POST_CASE(4) POST_CASE(5) POST_CASE(6) }
 #undef POST_CASE
   return ASVGP_ERR_UNSUPPORTED;

@@ -152,6 +152,41 @@ class _GPModelSurface:
         Ynew = np.asarray(Ynew.cpu() if isinstance(Ynew, torch.Tensor) else Ynew, dtype=np.float64).reshape(mean.shape)
         return _host(np.sum(-0.5 * (np.log(2 * np.pi * var) + (Ynew - mean) ** 2 / var), axis=-1))
 
+    # -- closed-form leave-one-out predictions (GPR_1d, and GPR_kron with d = 2) ---------------------------------------------
+    def _loo_unsupported(self, what):
+        raise NotImplementedError("%s.%s: closed-form leave-one-out predictions exist for GPR_1d and for GPR_kron with d = 2 only"
+                                  % (type(self).__name__, what))
+
+    def loo_predict_f_device(self):
+        self._loo_unsupported("loo_predict_f_device")
+
+    def loo_log_density_device(self):
+        self._loo_unsupported("loo_log_density_device")
+
+    def _loo_scores_device(self):
+        self._loo_unsupported("loo_scores")
+
+    def loo_predict_f(self):
+        """loo_predict_f_device as numpy: (mean (N, D), var (N, 1)) of f(x_i) given every training row but i."""
+        mean, var = self.loo_predict_f_device()
+        return mean.cpu().numpy(), var.cpu().numpy()
+
+    def loo_scores(self):
+        """Exact leave-one-out cross-validation scores over the rows with w_i > 0, as Python floats: n, log_density = sum_i log p(y_i | y_-i),
+        sq_err = sum_i sum_d (y_id - mean_id)^2, max_leverage = max_i h_i, and the derived nlpd = -log_density / n and
+        rmse = sqrt(sq_err / (n D)).  On a sharded model every rank streams its own rows against the global posterior; the sums are
+        all-reduced with SUM and the leverage with MAX, so every rank returns the global scores."""
+        sc = self._loo_scores_device()                      # device, 4 doubles: [n, log density, squared error, max leverage]
+        if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size(self._pg) > 1:
+            sums, mx = sc[:3].clone(), sc[3:].clone()
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self._pg)
+            dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=self._pg)
+            sc = torch.cat([sums, mx])
+        n, ld, sq, mx = sc.tolist()
+        D = self.y.shape[1]
+        return dict(n=n, log_density=ld, sq_err=sq, max_leverage=mx, nlpd=-ld / n if n else float("nan"),
+                    rmse=math.sqrt(sq / (n * D)) if n else float("nan"))
+
     def close(self):
         """Release the model's library handle now (pinned table ring, result mirror, plan) instead of at garbage collection."""
         h = getattr(self, "_h", None)
@@ -215,6 +250,8 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._out = torch.zeros(8, dtype=torch.float64, device=dev)
         self._info = torch.zeros(2, dtype=torch.int32, device=dev)
         self._post = None
+        self._post_loo = None                 # (theta, alpha, W, Pinv_band) of the leave-one-out methods
+        self._loo_ws = None
         self._post_cov = None                 # (theta, W_dense): the dense P^-1 - Kuu^-1 of predict_f_cov_device
         self._cov_ws = None
         self._host_result = np.zeros(10)      # [out[0..7], info[0], info[1]] of the last host-read evaluation
@@ -474,6 +511,64 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
                                            mean.data_ptr(), var.data_ptr(), stream_ptr()), "predict_1d")
         return mean, var
 
+    # -- leave-one-out predictions in closed form (not in the reference) ------------------------------------------------------
+    def _posterior_loo(self):
+        """asvgp_posterior_prepare_loo_1d once per theta: (alpha, W, Pinv_band), cached beside _post (whose alpha and W these are, bit for
+        bit); Pinv_band = band(P^-1) as the P chain leaves it."""
+        v, l, s = self.theta()
+        key = (v, l, s)
+        if self._post_loo is not None and self._post_loo[0] == key:
+            return self._post_loo[1:]
+        b = self.basis
+        k, M, D = self.bandwidth, b.m, self.D
+        dev = self._stats.device
+        alpha = torch.empty((M, D), dtype=torch.float64, device=dev)
+        W = torch.empty((k + 1, M), dtype=torch.float64, device=dev)
+        Pinv = torch.empty((k + 1, M), dtype=torch.float64, device=dev)
+        S = self._statics()
+        check(get_lib().asvgp_posterior_prepare_loo_1d(self._h.ptr, self._stats.data_ptr(), S.data_ptr(), self.kernel.kind, v, l, s, M, k,
+                                                       D, alpha.data_ptr(), W.data_ptr(), Pinv.data_ptr(), self._info.data_ptr(),
+                                                       self._elbo_ws.data_ptr(), self._elbo_ws.numel() * 8, stream_ptr()),
+              "posterior_prepare_loo_1d")
+        self._check_pd()
+        self._post_loo = (key, alpha, W, Pinv)
+        return alpha, W, Pinv
+
+    def _loo(self, want_mean=False, want_var=False, want_logdens=False, want_scores=False):
+        """asvgp_loo_1d over this rank's rows: (mean (N, D), var (N, 1), logdens (N,), scores (4,)), None where not asked for."""
+        alpha, W, Pinv = self._posterior_loo()
+        b = self.basis
+        lib = get_lib()
+        dev = self._stats.device
+        N = self.X.shape[0]
+        if self._loo_ws is None:
+            self._loo_ws = torch.empty(lib.asvgp_loo_workspace_bytes(b.m, b.order, self.D) // 8, dtype=torch.float64, device=dev)
+        mean = torch.empty((N, self.D), dtype=torch.float64, device=dev) if want_mean else None
+        var = torch.empty((N, 1), dtype=torch.float64, device=dev) if want_var else None
+        ld = torch.empty(N, dtype=torch.float64, device=dev) if want_logdens else None
+        sc = torch.empty(4, dtype=torch.float64, device=dev) if want_scores else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        check(lib.asvgp_loo_1d(self._h.ptr, self.X.data_ptr(), self.y.data_ptr(), ptr(self.weights), N, self.D, b.mesh.data_ptr(),
+                               b.mesh.shape[0], b.delta_np, b.order, b.m, alpha.data_ptr(), W.data_ptr(), Pinv.data_ptr(),
+                               float(self.kernel.variance), float(self.likelihood.variance), ptr(mean), ptr(var), ptr(ld), ptr(sc),
+                               self._loo_ws.data_ptr(), self._loo_ws.numel() * 8, stream_ptr()), "loo_1d")
+        return mean, var, ld, sc
+
+    def loo_predict_f_device(self):
+        """Mean (N, D) and variance (N, 1) of f(x_i) given every training row but i, for all rows of this model (this rank's rows of a
+        sharded one), as device tensors: one streaming kernel (asvgp_loo_1d), no refits.  A row with weight 0 is absent from the model
+        already: its entries are predict_f_device's."""
+        mean, var, _, _ = self._loo(want_mean=True, want_var=True)
+        return mean, var
+
+    def loo_log_density_device(self):
+        """log p(y_i | y_-i) (N,) as a device tensor, summed over the D outputs the way predict_log_density sums; the left-out
+        observation's noise variance is sigma2 / w_i (sigma2 for a row with weight 0)."""
+        return self._loo(want_logdens=True)[2]
+
+    def _loo_scores_device(self):
+        return self._loo(want_scores=True)[3]               # (nothing of size N is written: 24 B read per row, 16 B unweighted)
+
     # -- full posterior covariance (not in the reference: its predict_f(full_cov=True) raises, gpr.py:113) ------------
     def _posterior_cov(self):
         """asvgp_posterior_cov_prepare_1d once per theta: W_dense = P^-1 - Kuu^-1 (M x M, device), cached beside _post."""
@@ -597,6 +692,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
     def close(self):
         """Also releases the cached dense W and its workspace."""
         self._post_cov = None
+        self._post_loo = None
         self._cov_ws = None
         super().close()
 
@@ -1502,16 +1598,25 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         return mean, var[:, :1]
 
     def predict_f_device(self, Xnew, chunk=4096):
-        lib = get_lib()
         if self._dense_mode:
             return self._dense_predict(Xnew)
         key = self.theta()
         if self._post is None or self._post[0] != key:
             f = self._factor(want_alpha=False)
             self._post = (key, f, self._selinv(f))               # (also fills f["alpha"])
+        mean, qk, qp = self._point_moments(_to_device(Xnew, self._stats.device))
+        vprod = 1.0
+        for kern in self.kernels:
+            vprod *= float(kern.variance)
+        var = vprod + qp - qk
+        return mean.reshape(-1, 1), var.reshape(-1, 1)
+
+    def _point_moments(self, X):
+        """Per row of X (n, 2), from the cached factor and selected inverse (_post): mu = phi^T alpha, q_K = phi^T Kuu^-1 phi and
+        g = phi^T P^-1 phi, each (n,)."""
+        lib = get_lib()
         f, (SigD, SigS, Bb) = self._post[1], self._post[2]
         b1, b2 = self.bases
-        X = _to_device(Xnew, self._stats.device)
         n = X.shape[0]
         mean = torch.empty(n, dtype=torch.float64, device=X.device)
         qk = torch.empty(n, dtype=torch.float64, device=X.device)
@@ -1532,11 +1637,55 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
                                                        b2.mesh.data_ptr(), b2.mesh.shape[0], b2.delta_np, b1.m, b2.m, self.order,
                                                        SigD.data_ptr(), SigS.data_ptr(), Bb, lay["nb"], lay["top_end"], lay["padt"], lay["padb"],
                                                        qp.data_ptr(), stream_ptr()), "predict_kron2d_var_twisted")
+        return mean, qk, qp
+
+    # -- leave-one-out predictions in closed form (d = 2; not in the reference) ------------------------------------------------
+    def _loo(self):
+        """The formulas of asvgp_loo_1d (include/asvgp_hip.h) in torch on the device, over this rank's rows, from the existing per-point
+        kernels: asvgp_predict_kron2d gives mu and q_K, asvgp_predict_kron2d_var (or its twisted form, whichever layout _twist_layout()
+        chose) gives g.  Returns (mean (N, 1), var (N, 1), logdens (N,), h (N,), pos (N,) bool); nothing is clamped."""
+        key, lay = self.theta(), self._twist_layout()
+        if self._post is None or self._post[0] != key or self._post[1].get("twist") != lay:
+            f = self._factor(want_alpha=False)
+            self._post = (key, f, self._selinv(f))               # (also fills f["alpha"])
+        mu, qk, g = self._point_moments(self.X)
+        s = float(self.likelihood.variance)
         vprod = 1.0
         for kern in self.kernels:
             vprod *= float(kern.variance)
-        var = vprod + qp - qk
-        return mean.reshape(-1, 1), var.reshape(-1, 1)
+        y = self.y.reshape(-1)
+        if self.weights is None:
+            h, pos, noise = g / s, torch.ones_like(g, dtype=torch.bool), s
+        else:
+            w = self.weights
+            h, pos = w * g / s, w > 0
+            noise = torch.where(pos, s / torch.where(pos, w, torch.ones_like(w)), torch.full_like(w, s))
+        om = 1.0 - h
+        mean = (mu - h * y) / om
+        var = vprod + g - qk + g * (h / om)
+        s2 = var + noise
+        ld = -0.5 * (torch.log(2 * math.pi * s2) + (y - mean) ** 2 / s2)
+        return mean.reshape(-1, 1), var.reshape(-1, 1), ld, h, pos
+
+    def loo_predict_f_device(self):
+        """Mean (N, 1) and variance (N, 1) of f(x_i) given every training row but i (this rank's rows of a sharded model), as device
+        tensors; no refits.  A row with weight 0 is absent from the model already: its entries are predict_f_device's."""
+        self._require_2d("loo_predict_f_device")
+        return self._loo()[:2]
+
+    def loo_log_density_device(self):
+        """log p(y_i | y_-i) (N,) as a device tensor; the left-out observation's noise variance is sigma2 / w_i (sigma2 for weight 0)."""
+        self._require_2d("loo_log_density_device")
+        return self._loo()[2]
+
+    def _loo_scores_device(self):
+        self._require_2d("loo_scores")
+        mean, _, ld, h, pos = self._loo()
+        zero = torch.zeros((), dtype=torch.float64, device=ld.device)
+        sq = (self.y.reshape(-1) - mean.reshape(-1)) ** 2
+        # (sums over the rows with w > 0 only; a NaN leverage must reach max h, which amax propagates)
+        return torch.stack([pos.sum().to(torch.float64), torch.where(pos, ld, zero).sum(), torch.where(pos, sq, zero).sum(),
+                            torch.where(pos, h, zero).amax() if h.numel() else zero])
 
 
 class GPR_additive(_GPModelSurface, _ShardedStats):

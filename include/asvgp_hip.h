@@ -405,6 +405,49 @@ int asvgp_predict_cov_deriv_1d(asvgp_handle_t handle, const double* x1, int64_t 
                                double lengthscale, int p, int q, double* cov, int64_t ldc, asvgp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Leave-one-out predictions of GPR_1d in closed form (GPR_1d.loo_predict_f_device / loo_log_density_device / loo_scores; not in the
+ * reference).  The posterior is a Gaussian linear model in the inducing features, so removing training row i is a rank-one downdate of
+ * P = Kuu + Phi W Phi^T / s; with phi_i = phi(x_i) and the quantities prepared once per theta,
+ *   g_i   = phi_i^T P^-1 phi_i            (touches band(P^-1) only)
+ *   h_i   = w_i g_i / s                   (leverage, 0 <= h_i < 1; w_i = 1 without weights)
+ *   mu_i  = phi_i^T alpha,  var_i = variance + phi_i^T W phi_i      (the ordinary posterior of asvgp_predict_1d at x_i)
+ *   mean of f(x_i) given all rows but i:      (mu_i - h_i y_i) / (1 - h_i)
+ *   variance of f(x_i) given all rows but i:  var_i + g_i h_i / (1 - h_i)
+ *   log p(y_i | y_-i) = sum_d log N(y_id | that mean, that variance + s / w_i)
+ * so all N leave-one-out predictions cost one streaming pass over the training rows.
+ * posterior_prepare_loo: asvgp_posterior_prepare_1d (the same alpha and W, bit for bit; the same info and workspace rules) with one more
+ * output, Pinv_band (k+1, M): band(P^-1) as the P chain leaves it, in the lower-band layout of W.  (Not W + band(Kuu^-1): that sum loses
+ * every digit of P^-1 below 1e-16 |Kuu^-1|, exactly where the data are informative.)
+ * loo: x (N), y (N, D) row-major and w (N, or NULL: all ones) are the TRAINING rows; whatever asvgp_phi_accumulate_1d_weighted accepts is
+ * accepted (orders 1..6, any M, D >= 1, float32-linspace meshes, any 8-byte alignment, any input order).  Outputs, each nullable, at least
+ * one asked for: mean (N, D), var (N), logdens (N) (summed over the D outputs) and scores (4 doubles, overwritten) =
+ * [#{w_i > 0}, sum logdens, sum_i sum_d (y_id - mean_id)^2, max_i h_i], the sums and the maximum over the rows with w_i > 0 (max h = 0 when
+ * there are none).  A row with w_i = 0 is already absent from the model (h_i = 0): its per-row outputs are the ordinary prediction, its
+ * log density takes noise variance s, and it is left out of the scores.  Nothing is clamped: if rounding pushes 1 - h_i to <= 0 the
+ * row's outputs are the infinities or NaNs the formulas give, and max h reports it.
+ * One kernel, templated on the order: per point the B-spline pieces once, the D dot products and both quadratic forms on the
+ * (k+1) x (k+1) window.  From N = 65 536 on alpha, the mesh and W / Pinv_band (interleaved: one 16-byte read per band position) are
+ * staged in LDS; tables that do not fit whole (k = 4, D = 1: M > 1696) are split into up to 4 ranges of mesh cells (2 for orders 5 and 6),
+ * each range's workgroups striding over all rows and taking the rows of their cells.  Otherwise the tables are read through the caches.
+ * A grid of at most 262 144 threads per range strides over the rows.  The scores
+ * are reduced in a fixed order without floating-point atomics (per wavefront, per workgroup into the workspace, then a one-wavefront
+ * launch): the same call made twice returns bit-identical scores.  With mean, var and logdens NULL nothing of size N is written: that
+ * pass reads 24 B per point (16 B unweighted).
+ * N = 0: ASVGP_OK, nothing launched, scores zeroed.  ASVGP_ERR_BAD_ARG for a NULL required pointer, a negative size,
+ * n_mesh != M - order + 1, D < 1, a non-positive variance or noise variance, or all four outputs NULL; ASVGP_ERR_UNSUPPORTED for an order
+ * outside 1..6; ASVGP_ERR_WORKSPACE for a workspace shorter than asvgp_loo_workspace_bytes.  The handle may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+int asvgp_posterior_prepare_loo_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
+                                   double lengthscale, double noise_variance, int64_t M, int k, int64_t D,
+                                   double* alpha, double* W, double* Pinv_band, int* info, void* workspace, size_t workspace_bytes,
+                                   asvgp_stream_t stream);
+size_t asvgp_loo_workspace_bytes(int64_t M, int order, int64_t D);
+int asvgp_loo_1d(asvgp_handle_t handle, const double* x, const double* y, const double* w, int64_t N, int64_t D, const double* mesh,
+                 int64_t n_mesh, double delta, int order, int64_t M, const double* alpha, const double* W, const double* Pinv_band,
+                 double variance, double noise_variance, double* mean, double* var, double* logdens, double* scores,
+                 void* workspace, size_t workspace_bytes, asvgp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 2-D Kronecker (tensor-product) path   replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
  * linear algebra of GPR_kron gpr.py:239-359 (KufKfu.todense(), tf.linalg.cholesky / triangular_solve / cholesky_solve).
  * Basis pair (i1, i2) has row index i1*m2 + i2 (dim-0 major, as make_kvs_two_sparse).  Both bases share `order` = k
