@@ -77,6 +77,8 @@ SIGNATURES = {
     "asvgp_posterior_prepare_loo_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _I, _L, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_loo_workspace_bytes": (_Z, [_L, _I, _L]),
     "asvgp_loo_1d": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _Z, _P]),
+    "asvgp_score_workspace_bytes": (_Z, [_L, _I, _L]),
+    "asvgp_score_1d": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _D, _D, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_predict_1d": (_I, [_P, _L, _P, _L, _D, _I, _L, _P, _P, _D, _L, _P, _P, _P]),
     "asvgp_predict_1d_h": (_I, [_P, _P, _L, _P, _L, _D, _I, _L, _P, _P, _D, _L, _P, _P, _P]),
     "asvgp_posterior_cov_workspace_bytes": (_Z, [_L, _I, _L]),

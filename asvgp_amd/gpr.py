@@ -66,6 +66,58 @@ def _predictive_weights(weights, n):
     return w
 
 
+def _prepare_heldout(data, weights, ncol, D, dev, what):
+    """Held-out rows (Xnew (n, ncol), Ynew (n, D)) and their weights -> fp64 device tensors (X (n, ncol), Y (n, D), w (n,) or None),
+    validated before anything is launched: ValueError for a wrong number of columns or rows, or a weight that is not finite and >= 0."""
+    Xnew, Ynew = data
+    X = _to_device(Xnew, dev)
+    if X.dim() == 1 and ncol == 1:
+        X = X.reshape(-1, 1)
+    if X.dim() != 2 or X.shape[1] != ncol:
+        raise ValueError("%s: Xnew must have shape (n, %d); got %s" % (what, ncol, tuple(X.shape)))
+    n = X.shape[0]
+    Y = _to_device(Ynew, dev)
+    if Y.dim() == 1 and D == 1:
+        Y = Y.reshape(-1, 1)
+    if Y.dim() != 2 or tuple(Y.shape) != (n, D):
+        raise ValueError("%s: Ynew must have shape (%d, %d), one row per row of Xnew; got %s" % (what, n, D, tuple(Y.shape)))
+    w = None if weights is None else _prepare_weights(weights, n, dev, what)
+    return X.contiguous(), Y.contiguous(), w
+
+
+def _prepare_folds(folds, n, weights, dev, what):
+    """Fold labels of this rank's n rows -> (int64 device tensor (n,), per-fold count of rows with positive weight (K_local,) int64).
+    ValueError for a wrong shape, a label that is not an integer, or a negative label."""
+    f = torch.as_tensor(folds)
+    if f.dim() == 2 and f.shape[1] == 1:
+        f = f.reshape(-1)
+    if f.dim() != 1 or f.shape[0] != n:
+        raise ValueError("%s: folds must have shape (N,) with N = %d rows; got %s" % (what, n, tuple(f.shape)))
+    if f.dtype.is_floating_point or f.dtype == torch.bool or f.dtype.is_complex:
+        raise ValueError("%s: folds must be an integer array; got %s" % (what, f.dtype))
+    f = f.to(device=dev, dtype=torch.int64).contiguous()
+    if n and int(f.min().item()) < 0:
+        i = int(torch.nonzero(f < 0)[0].item())
+        raise ValueError("%s: folds must be >= 0; row %d has fold %d" % (what, i, int(f[i].item())))
+    pos = f if weights is None else f[weights > 0]
+    counts = torch.bincount(pos, minlength=(int(f.max().item()) + 1) if n else 0)
+    return f, counts
+
+
+def _require_folds_populated(counts, what):
+    empty = torch.nonzero(counts <= 0)
+    if counts.numel() == 0 or empty.numel():
+        raise ValueError("%s: %s" % (what, "no folds" if counts.numel() == 0 else
+                                     "fold %d has no row of positive weight" % int(empty[0].item())))
+
+
+def _score_dict(n, ld, sq, chi, D):
+    """The held-out scores as Python floats, with the derived nlpd, rmse and mean_chi2 (NaN for an empty set)."""
+    nan = float("nan")
+    return dict(n=n, log_density=ld, sq_err=sq, chi2=chi, nlpd=-ld / n if n else nan, rmse=math.sqrt(sq / (n * D)) if n else nan,
+                mean_chi2=chi / (n * D) if n else nan)
+
+
 class _ShardedStats:
     """N-sharded statistics: every (re)run of the local Phi pass is followed by the ONE all-reduce of the
     packed buffer, so `_stats` (and the views KufKfu / Kuf_y / tr_yTy into it) are always the global sums."""
@@ -187,6 +239,156 @@ class _GPModelSurface:
         return dict(n=n, log_density=ld, sq_err=sq, max_leverage=mx, nlpd=-ld / n if n else float("nan"),
                     rmse=math.sqrt(sq / (n * D)) if n else float("nan"))
 
+    # -- held-out scores on the device (every model class; GPR_1d fuses them into one kernel) ------------------------------
+    def _is_sharded(self):
+        return bool(self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size(self._pg) > 1)
+
+    def _heldout(self, data, weights, what):
+        return _prepare_heldout(data, weights, self.X.shape[1], self.y.shape[1], self._stats.device, "%s.%s" % (type(self).__name__, what))
+
+    def _noise_column(self, w, n):
+        """sigma2 / w_i as an (n, 1) device column (sigma2 for a row with weight 0), or the float sigma2 without weights"""
+        s = float(self.likelihood.variance)
+        if w is None:
+            return s
+        pos, sv = w > 0, torch.full_like(w, s)
+        return torch.where(pos, sv / torch.where(pos, w, torch.ones_like(w)), sv).reshape(n, 1)   # (tensor / tensor: a true division)
+
+    def predict_y_device(self, Xnew, weights=None):
+        """predict_y on the device: (mean (n, D), var_f + sigma2 / w (n, 1)) as device tensors, nothing copied to the host.  weights: per-row
+        w of the NEW rows, finite and >= 0 (a row with weight 0 takes noise variance sigma2)."""
+        what = "%s.predict_y_device" % type(self).__name__
+        dev = self._stats.device
+        X = _to_device(Xnew, dev)
+        if X.dim() == 1 and self.X.shape[1] == 1:
+            X = X.reshape(-1, 1)
+        if X.dim() != 2 or X.shape[1] != self.X.shape[1]:
+            raise ValueError("%s: Xnew must have shape (n, %d); got %s" % (what, self.X.shape[1], tuple(X.shape)))
+        w = None if weights is None else _prepare_weights(weights, X.shape[0], dev, what)
+        mean, var = self.predict_f_device(X)
+        return mean, var + self._noise_column(w, X.shape[0])
+
+    def _heldout_moments(self, X, Y, w):
+        """(mean (n, D), s2 (n, 1), squared error (n,), logdens (n,)) of validated held-out rows, composed in torch on the device"""
+        mean, var = self.predict_f_device(X)
+        s2 = var + self._noise_column(w, X.shape[0])
+        sq = ((Y - mean) ** 2).sum(-1)
+        ld = -0.5 * (Y.shape[1] * torch.log(2 * math.pi * s2.reshape(-1)) + sq / s2.reshape(-1))
+        return mean, s2, sq, ld
+
+    def predict_log_density_device(self, data, weights=None):
+        """predict_log_density on the device: sum_d log N(y_id | mean_id, var_f + sigma2 / w_i) as a device tensor (n,); data = (Xnew, Ynew).
+        Nothing of size n is copied to the host."""
+        X, Y, w = self._heldout(data, weights, "predict_log_density_device")
+        return self._heldout_moments(X, Y, w)[3]
+
+    def _score_device(self, X, Y, w):
+        """[#{w > 0}, sum logdens, sum squared error, sum squared error / s2] over the rows with w > 0: device, 4 doubles"""
+        _, s2, sq, ld = self._heldout_moments(X, Y, w)
+        if w is None:
+            return torch.stack([torch.tensor(float(X.shape[0]), dtype=torch.float64, device=ld.device), ld.sum(), sq.sum(), (sq / s2.reshape(-1)).sum()])
+        pos = w > 0
+        zero = torch.zeros((), dtype=torch.float64, device=ld.device)
+        return torch.stack([pos.sum().to(torch.float64), torch.where(pos, ld, zero).sum(), torch.where(pos, sq, zero).sum(),
+                            torch.where(pos, sq / s2.reshape(-1), zero).sum()])
+
+    def score(self, data, weights=None):
+        """Scores of held-out rows data = (Xnew, Ynew) as Python floats: n = #{w_i > 0}, log_density = sum_i log p(y_i), sq_err =
+        sum_i sum_d (y_id - mean_id)^2, chi2 = sum_i sum_d (y_id - mean_id)^2 / (var_i + sigma2 / w_i) (expectation n D), and the derived
+        nlpd = -log_density / n, rmse = sqrt(sq_err / (n D)), mean_chi2 = chi2 / (n D) (NaN for n = 0).  Rows with weight 0 are left out.
+        Everything of size n stays on the device.  On a sharded model each rank scores the rows it is given against the global posterior
+        and the four sums are all-reduced with SUM, so every rank returns the global scores."""
+        X, Y, w = self._heldout(data, weights, "score")
+        return self._score_floats(X, Y, w)
+
+    def _score_floats(self, X, Y, w):
+        sc = self._score_device(X, Y, w)
+        if self._is_sharded():
+            sc = sc.clone()
+            dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=self._pg)
+        n, ld, sq, chi = sc.tolist()
+        return _score_dict(n, ld, sq, chi, self.y.shape[1])
+
+    # -- changing the weights in place, and K-fold cross-validation (GPR_1d, and GPR_kron with d = 2) -----------------------
+    def _weights_unsupported(self, what):
+        raise NotImplementedError("%s.%s: per-observation weights exist for GPR_1d and for GPR_kron with d = 2 only"
+                                  % (type(self).__name__, what))
+
+    def set_weights(self, weights):
+        self._weights_unsupported("set_weights")
+
+    def kfold_scores(self, folds, refit=False, maxiter=None):
+        self._weights_unsupported("kfold_scores")
+
+    def _set_weights_checked(self, weights):
+        """set_weights of the models that have a weighted Phi pass: validate like the constructor, copy into the existing weights tensor,
+        re-run the weighted pass over this rank's rows (+ the usual all-reduce), refresh the counts, drop the theta-keyed caches."""
+        name = type(self).__name__
+        if self.weights is None:
+            raise ValueError("%s.set_weights: this model was built without weights (pass weights= to the constructor)" % name)
+        w = _prepare_weights(weights, self.X.shape[0], self._stats.device, "%s.set_weights" % name)
+        self._apply_weights(w)
+
+    def _kfold_state(self):
+        """what kfold_scores changes, cloned: restored by copy, because the weighted Phi pass accumulates with atomics"""
+        return dict(stats=self._stats.clone(), weights=self.weights.clone(), wstats=self._wstats.clone(),
+                    sums=(self.num_data, self.weight_sum, self.log_weight_sum))
+
+    def _kfold_restore(self, st):
+        self._stats.copy_(st["stats"])
+        self._wstats.copy_(st["wstats"])
+        self._restore_weights(st["weights"])
+        self.num_data, self.weight_sum, self.log_weight_sum = st["sums"]
+        h = getattr(self, "_h", None)
+        if h is not None:
+            h.set_weight_sums(self.num_data, self.weight_sum, self.log_weight_sum)
+        self._drop_theta_caches()
+
+    def _kfold_scores(self, folds, refit, maxiter):
+        name = "%s.kfold_scores" % type(self).__name__
+        dev = self._stats.device
+        fold, counts = _prepare_folds(folds, self.X.shape[0], self.weights, dev, name)
+        if self._is_sharded():                                  # K and the per-fold counts are global
+            K = torch.tensor([counts.numel()], dtype=torch.int64, device=dev)
+            dist.all_reduce(K, op=dist.ReduceOp.MAX, group=self._pg)
+            full = torch.zeros(int(K.item()), dtype=torch.int64, device=dev)
+            full[:counts.numel()] = counts
+            dist.all_reduce(full, op=dist.ReduceOp.SUM, group=self._pg)
+            counts = full
+        _require_folds_populated(counts, name)
+        K = counts.numel()
+        twin = self._weighted_twin() if self.weights is None else None
+        m = self if twin is None else twin
+        params = self.trainable_parameters
+        theta0 = [(p._u, p._value) for p in params]
+
+        def reset_theta():
+            for p, (u, v) in zip(params, theta0):
+                p._u, p._value = u, v
+
+        state = m._kfold_state()
+        w0, zero = state["weights"], torch.zeros((), dtype=torch.float64, device=dev)
+        out = []
+        try:
+            for f in range(K):
+                inside = fold == f
+                m._apply_weights(torch.where(inside, zero, w0))
+                if refit:
+                    reset_theta()
+                    m.fit(**({} if maxiter is None else {"maxiter": maxiter}))
+                    m._drop_theta_caches()
+                sc = m._score_floats(m.X, m.y, torch.where(inside, w0, zero))
+                if refit:
+                    sc["theta"] = m.theta()
+                out.append(sc)
+        finally:
+            reset_theta()
+            m._kfold_restore(state)
+            if twin is not None:
+                twin.close()
+        n, ld, sq, chi = (sum(s[k] for s in out) for k in ("n", "log_density", "sq_err", "chi2"))
+        return dict(folds=out, total=_score_dict(n, ld, sq, chi, self.y.shape[1]))
+
     def close(self):
         """Release the model's library handle now (pinned table ring, result mirror, plan) instead of at garbage collection."""
         h = getattr(self, "_h", None)
@@ -252,6 +454,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._post = None
         self._post_loo = None                 # (theta, alpha, W, Pinv_band) of the leave-one-out methods
         self._loo_ws = None
+        self._score_ws = None                 # workgroup records of asvgp_score_1d (allocated on first use)
         self._post_cov = None                 # (theta, W_dense): the dense P^-1 - Kuu^-1 of predict_f_cov_device
         self._cov_ws = None
         self._host_result = np.zeros(10)      # [out[0..7], info[0], info[1]] of the last host-read evaluation
@@ -569,6 +772,70 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
     def _loo_scores_device(self):
         return self._loo(want_scores=True)[3]               # (nothing of size N is written: 24 B read per row, 16 B unweighted)
 
+    # -- held-out scores in one streaming pass (asvgp_score_1d; not in the reference) ------------------------------------------
+    def _score_call(self, X, Y, w, want_logdens=False, want_scores=False):
+        """asvgp_score_1d over validated held-out rows: (logdens (n,), scores (4,)), None where not asked for"""
+        alpha, W = self._posterior()
+        b = self.basis
+        lib = get_lib()
+        dev = self._stats.device
+        n = X.shape[0]
+        if self._score_ws is None:
+            self._score_ws = torch.empty(lib.asvgp_score_workspace_bytes(b.m, b.order, self.D) // 8, dtype=torch.float64, device=dev)
+        ld = torch.empty(n, dtype=torch.float64, device=dev) if want_logdens else None
+        sc = torch.empty(4, dtype=torch.float64, device=dev) if want_scores else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        check(lib.asvgp_score_1d(self._h.ptr, X.data_ptr(), Y.data_ptr(), ptr(w), n, self.D, b.mesh.data_ptr(), b.mesh.shape[0], b.delta_np,
+                                 b.order, b.m, alpha.data_ptr(), W.data_ptr(), float(self.kernel.variance), float(self.likelihood.variance),
+                                 None, None, ptr(ld), ptr(sc), self._score_ws.data_ptr(), self._score_ws.numel() * 8, stream_ptr()), "score_1d")
+        return ld, sc
+
+    def predict_log_density_device(self, data, weights=None):
+        """sum_d log N(y_id | mean_id, var_f + sigma2 / w_i) as a device tensor (n,), data = (Xnew, Ynew): one streaming kernel
+        (asvgp_score_1d; 16 B in per row, 24 B weighted, 8 B out)."""
+        X, Y, w = self._heldout(data, weights, "predict_log_density_device")
+        return self._score_call(X, Y, w, want_logdens=True)[0]
+
+    def _score_device(self, X, Y, w):
+        return self._score_call(X, Y, w, want_scores=True)[1]      # (nothing of size n is written)
+
+    def _drop_theta_caches(self):
+        self._post = self._post_loo = self._post_cov = None
+
+    def _restore_weights(self, w):
+        self.weights.copy_(w)
+
+    def _apply_weights(self, w):
+        """validated weights (device, (N,)) into the existing tensor, then what the constructor does after its Phi pass"""
+        self.weights.copy_(w)
+        self._phi_pass_local()
+        if self._h.deferred and self._distributed:
+            check(get_lib().asvgp_phi_reduce_1d(self._h.ptr, stream_ptr()), "phi_reduce_1d")
+        self._set_weight_sums(self.num_data_local, self._wstats, self._pg)
+        self._h.set_weight_sums(self.num_data, self.weight_sum, self.log_weight_sum)
+        self._drop_theta_caches()
+
+    def set_weights(self, weights):
+        """Replace the per-observation weights of a model built with weights= (a new mask or fold) without rebuilding it: the handle, the
+        workspaces and the buffers stay; one weighted Phi pass over this rank's rows and the usual all-reduce."""
+        self._set_weights_checked(weights)
+
+    def _weighted_twin(self):
+        """this model with w = 1 through the weighted pass: shares X, y, the basis, the kernel and the likelihood objects"""
+        twin = GPR_1d((self.X, self.y), self.kernel, self.basis, process_group=self._pg, distributed=self._distributed,
+                      weights=torch.ones(self.X.shape[0], dtype=torch.float64, device=self._stats.device))
+        twin.likelihood = self.likelihood
+        return twin
+
+    def kfold_scores(self, folds, refit=False, maxiter=None):
+        """K-fold cross-validation.  folds: int array (N,) over this rank's rows with values 0..K-1 (K = max + 1, global on a sharded model).
+        For every fold f the model is conditioned on the weights w [fold != f] and the rows of the fold are scored with w [fold == f] - at the
+        model's current theta, or with refit=True after fit() started from it (the fold's fitted theta is reported as "theta").  Returns
+        dict(folds=[score() dict per fold], total=the scores of the summed n, log_density, sq_err, chi2).  On return, normal or by
+        exception, the model's weights, statistics, weight sums and theta are the ones it had, bit for bit.  A model built without weights
+        runs on an internal weighted twin with w = 1."""
+        return self._kfold_scores(folds, refit, maxiter)
+
     # -- full posterior covariance (not in the reference: its predict_f(full_cov=True) raises, gpr.py:113) ------------
     def _posterior_cov(self):
         """asvgp_posterior_cov_prepare_1d once per theta: W_dense = P^-1 - Kuu^-1 (M x M, device), cached beside _post."""
@@ -694,6 +961,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._post_cov = None
         self._post_loo = None
         self._cov_ws = None
+        self._score_ws = None
         super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False, batch=False):
@@ -1065,6 +1333,7 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
         start[1:] = torch.cumsum(counts, 0)
         Xs, ys = self.X[order].contiguous(), self.y[order].contiguous()
         if self.weights is not None:
+            self._sort_perm = order                               # (kept: set_weights regathers the sorted weights, no new argsort)
             return Xs, ys, start, self.weights[order].contiguous()
         if getattr(self, "_fp32_storage", False):
             Xs, ys = Xs.to(torch.float32), ys.to(torch.float32)   # (exact: the data WERE fp32)
@@ -1638,6 +1907,44 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
                                                        SigD.data_ptr(), SigS.data_ptr(), Bb, lay["nb"], lay["top_end"], lay["padt"], lay["padb"],
                                                        qp.data_ptr(), stream_ptr()), "predict_kron2d_var_twisted")
         return mean, qk, qp
+
+    # -- changing the weights in place and K-fold cross-validation (d = 2).  Held-out scores take the surface's composition: its
+    # predict_f_device is _point_moments (the two kernels that are the cost) plus an elementwise tail -------------------------------
+    def _drop_theta_caches(self):
+        self._post = self._post_cov = None
+
+    def _restore_weights(self, w):
+        self.weights.copy_(w)
+        if getattr(self, "_sorted", None) is not None:
+            torch.index_select(self.weights, 0, self._sort_perm, out=self._sorted[3])
+
+    def _apply_weights(self, w):
+        """validated weights (device, (N,)) into the existing tensors - the sort permutation is kept, only the sorted weights are
+        regathered - then what the constructor does after its Phi pass"""
+        self._restore_weights(w)
+        self._phi_pass_local()
+        self._set_weight_sums(self.n, self._wstats, self._pg)
+        self._drop_theta_caches()
+
+    def set_weights(self, weights):
+        """Replace the per-observation weights of a model built with weights= without rebuilding it: the cell sort of the rows is kept
+        (no new argsort), one weighted Phi pass over this rank's rows and the usual all-reduce."""
+        if self._dense_mode:
+            self._weights_unsupported("set_weights")
+        self._set_weights_checked(weights)
+
+    def _weighted_twin(self):
+        twin = GPR_kron((self.X, self.y), self.kernels, self.bases, process_group=self._pg, distributed=self._distributed,
+                        weights=torch.ones(self.n, dtype=torch.float64, device=self._stats.device))
+        twin.likelihood = self.likelihood
+        twin.twisted = self.twisted
+        return twin
+
+    def kfold_scores(self, folds, refit=False, maxiter=None):
+        """GPR_1d.kfold_scores for the d = 2 model (same arguments, same result, same guarantees)."""
+        if self._dense_mode:
+            self._weights_unsupported("kfold_scores")
+        return self._kfold_scores(folds, refit, maxiter)
 
     # -- leave-one-out predictions in closed form (d = 2; not in the reference) ------------------------------------------------
     def _loo(self):

@@ -448,7 +448,31 @@ int asvgp_loo_1d(asvgp_handle_t handle, const double* x, const double* y, const 
                  void* workspace, size_t workspace_bytes, asvgp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * 2-D Kronecker (tensor-product) path   replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
+ * Held-out scores (not in the reference, whose predict_log_density finishes on the host): GPR_1d.score / predict_log_density_device.
+ * x (N), y (N, D) row-major and w (N, or NULL: all ones) are rows the model has NOT seen, in any order and at any 8-byte alignment; alpha
+ * and W are the outputs of asvgp_posterior_prepare_1d.  Per row, with phi = phi(x_i):
+ *   mu = phi^T alpha,  var = v + phi^T W phi  (asvgp_predict_1d_h's moments, x treated as that entry treats it),
+ *   s2 = var + s / w_i  (s when w_i = 0),  logdens = sum_d log N(y_id | mu_d, s2).
+ * Outputs, each nullable, at least one asked for: mean (N, D), var (N), logdens (N) and scores (4 doubles, overwritten) =
+ * [#{w_i > 0}, sum logdens, sum_i sum_d (y_id - mu_id)^2, sum_i sum_d (y_id - mu_id)^2 / s2_i] over the rows with w_i > 0 (the fourth is the
+ * calibration statistic: its expectation is n D).  A row with w_i = 0 gets its per-row outputs and is left out of the scores.  Nothing is
+ * clamped: a NaN in a counted row reaches the sums.
+ * One kernel, templated on the order, by asvgp_loo_1d's plan with one band: from N = 65 536 on W, alpha and the mesh are staged in LDS,
+ * whole while 8 ((k+1) M + M D + n_mesh + 64) bytes fit 160 KiB - 512 (k = 4, D = 1: M <= 2907), else split into up to 4 ranges of mesh
+ * cells (2 for orders 5 and 6); otherwise the tables are read through the caches.  A grid of at most 262 144 threads per range strides over
+ * the rows.  The scores are reduced in a fixed order without floating-point atomics (per wavefront, per workgroup into the workspace, then
+ * a one-wavefront launch): the same call twice returns the same bits, and the scores-only call (nothing of size N written) the bits of the
+ * per-row call.
+ * Return codes and argument rules are asvgp_loo_1d's (N = 0: ASVGP_OK, nothing launched, scores zeroed; the handle may be NULL).
+ * ---------------------------------------------------------------------------------------------- */
+size_t asvgp_score_workspace_bytes(int64_t M, int order, int64_t D);
+int asvgp_score_1d(asvgp_handle_t handle, const double* x, const double* y, const double* w, int64_t N, int64_t D, const double* mesh,
+                   int64_t n_mesh, double delta, int order, int64_t M, const double* alpha, const double* W, double variance,
+                   double noise_variance, double* mean, double* var, double* logdens, double* scores, void* workspace,
+                   size_t workspace_bytes, asvgp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2-D Kronecker (tensor-product) path  replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
  * linear algebra of GPR_kron gpr.py:239-359 (KufKfu.todense(), tf.linalg.cholesky / triangular_solve / cholesky_solve).
  * Basis pair (i1, i2) has row index i1*m2 + i2 (dim-0 major, as make_kvs_two_sparse).  Both bases share `order` = k
  * (gpr.py:261 takes bases[0].order).  X: (N, 2) row-major, 16-byte aligned.
