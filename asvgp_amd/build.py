@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libasvgp_hip.so")
 SOURCES = ["phi_pass.hip", "band_ops.hip", "elbo.hip", "kron.hip", "additive.hip", "handle.hip", "prior_dd.hip", "posterior_cov.hip", "posterior_cov_kron.hip",
-           "posterior_cov_additive.hip", "loo.hip", "score.hip"]
+           "posterior_cov_additive.hip", "row_scores.hip"]
 EXTRA = {"prior_dd.hip": ["-ffp-contract=off"]}   # error-free transforms: nothing may be fused or re-associated
 HOST_SOURCES = ["prior_plan.cpp"]   # plain C++ (host planner of the prior chain): no FMA contraction, see prior_plan.cpp
 ELBO_KS = (1, 2, 3, 4, 5, 6)

@@ -453,8 +453,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._info = torch.zeros(2, dtype=torch.int32, device=dev)
         self._post = None
         self._post_loo = None                 # (theta, alpha, W, Pinv_band) of the leave-one-out methods
-        self._loo_ws = None
-        self._score_ws = None                 # workgroup records of asvgp_score_1d (allocated on first use)
+        self._loo_ws = self._score_ws = None  # workgroup records of asvgp_loo_1d / asvgp_score_1d (allocated on first use)
         self._post_cov = None                 # (theta, W_dense): the dense P^-1 - Kuu^-1 of predict_f_cov_device
         self._cov_ws = None
         self._host_result = np.zeros(10)      # [out[0..7], info[0], info[1]] of the last host-read evaluation
@@ -737,25 +736,32 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._post_loo = (key, alpha, W, Pinv)
         return alpha, W, Pinv
 
-    def _loo(self, want_mean=False, want_var=False, want_logdens=False, want_scores=False):
-        """asvgp_loo_1d over this rank's rows: (mean (N, D), var (N, 1), logdens (N,), scores (4,)), None where not asked for."""
-        alpha, W, Pinv = self._posterior_loo()
+    def _row_scores(self, entry, X, Y, w, tables, want_mean, want_var, want_logdens, want_scores):
+        """asvgp_loo_1d / asvgp_score_1d (entry = "loo" / "score") over the n rows X, Y, w against the posterior tables (alpha, W and, for
+        "loo", Pinv_band): (mean (n, D), var (n, 1), logdens (n,), scores (4,)), None where not asked for.  (Plain statements on
+        purpose: this runs on the host ahead of a kernel of 0.1 ms, where a generic loop over the outputs shows in the probes.)"""
         b = self.basis
         lib = get_lib()
         dev = self._stats.device
-        N = self.X.shape[0]
-        if self._loo_ws is None:
-            self._loo_ws = torch.empty(lib.asvgp_loo_workspace_bytes(b.m, b.order, self.D) // 8, dtype=torch.float64, device=dev)
-        mean = torch.empty((N, self.D), dtype=torch.float64, device=dev) if want_mean else None
-        var = torch.empty((N, 1), dtype=torch.float64, device=dev) if want_var else None
-        ld = torch.empty(N, dtype=torch.float64, device=dev) if want_logdens else None
+        n = X.shape[0]
+        ws = getattr(self, "_%s_ws" % entry)      # workgroup records, allocated on first use; one per entry point: their streams may differ
+        if ws is None:
+            ws = torch.empty(getattr(lib, "asvgp_%s_workspace_bytes" % entry)(b.m, b.order, self.D) // 8, dtype=torch.float64, device=dev)
+            setattr(self, "_%s_ws" % entry, ws)
+        mean = torch.empty((n, self.D), dtype=torch.float64, device=dev) if want_mean else None
+        var = torch.empty((n, 1), dtype=torch.float64, device=dev) if want_var else None
+        ld = torch.empty(n, dtype=torch.float64, device=dev) if want_logdens else None
         sc = torch.empty(4, dtype=torch.float64, device=dev) if want_scores else None
         ptr = lambda t: None if t is None else t.data_ptr()
-        check(lib.asvgp_loo_1d(self._h.ptr, self.X.data_ptr(), self.y.data_ptr(), ptr(self.weights), N, self.D, b.mesh.data_ptr(),
-                               b.mesh.shape[0], b.delta_np, b.order, b.m, alpha.data_ptr(), W.data_ptr(), Pinv.data_ptr(),
-                               float(self.kernel.variance), float(self.likelihood.variance), ptr(mean), ptr(var), ptr(ld), ptr(sc),
-                               self._loo_ws.data_ptr(), self._loo_ws.numel() * 8, stream_ptr()), "loo_1d")
+        check(getattr(lib, "asvgp_%s_1d" % entry)(self._h.ptr, X.data_ptr(), Y.data_ptr(), ptr(w), n, self.D, b.mesh.data_ptr(), b.mesh.shape[0],
+                                                  b.delta_np, b.order, b.m, *[t.data_ptr() for t in tables], float(self.kernel.variance),
+                                                  float(self.likelihood.variance), ptr(mean), ptr(var), ptr(ld), ptr(sc), ws.data_ptr(),
+                                                  ws.numel() * 8, stream_ptr()), entry + "_1d")
         return mean, var, ld, sc
+
+    def _loo(self, want_mean=False, want_var=False, want_logdens=False, want_scores=False):
+        """asvgp_loo_1d over this rank's rows: (mean (N, D), var (N, 1), logdens (N,), scores (4,)), None where not asked for."""
+        return self._row_scores("loo", self.X, self.y, self.weights, self._posterior_loo(), want_mean, want_var, want_logdens, want_scores)
 
     def loo_predict_f_device(self):
         """Mean (N, D) and variance (N, 1) of f(x_i) given every training row but i, for all rows of this model (this rank's rows of a
@@ -775,20 +781,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
     # -- held-out scores in one streaming pass (asvgp_score_1d; not in the reference) ------------------------------------------
     def _score_call(self, X, Y, w, want_logdens=False, want_scores=False):
         """asvgp_score_1d over validated held-out rows: (logdens (n,), scores (4,)), None where not asked for"""
-        alpha, W = self._posterior()
-        b = self.basis
-        lib = get_lib()
-        dev = self._stats.device
-        n = X.shape[0]
-        if self._score_ws is None:
-            self._score_ws = torch.empty(lib.asvgp_score_workspace_bytes(b.m, b.order, self.D) // 8, dtype=torch.float64, device=dev)
-        ld = torch.empty(n, dtype=torch.float64, device=dev) if want_logdens else None
-        sc = torch.empty(4, dtype=torch.float64, device=dev) if want_scores else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        check(lib.asvgp_score_1d(self._h.ptr, X.data_ptr(), Y.data_ptr(), ptr(w), n, self.D, b.mesh.data_ptr(), b.mesh.shape[0], b.delta_np,
-                                 b.order, b.m, alpha.data_ptr(), W.data_ptr(), float(self.kernel.variance), float(self.likelihood.variance),
-                                 None, None, ptr(ld), ptr(sc), self._score_ws.data_ptr(), self._score_ws.numel() * 8, stream_ptr()), "score_1d")
-        return ld, sc
+        return self._row_scores("score", X, Y, w, self._posterior(), False, False, want_logdens, want_scores)[2:]
 
     def predict_log_density_device(self, data, weights=None):
         """sum_d log N(y_id | mean_id, var_f + sigma2 / w_i) as a device tensor (n,), data = (Xnew, Ynew): one streaming kernel
@@ -961,7 +954,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._post_cov = None
         self._post_loo = None
         self._cov_ws = None
-        self._score_ws = None
+        self._loo_ws = self._score_ws = None
         super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False, batch=False):

@@ -11,7 +11,7 @@ applied to the kernel's own (mean, var): 1e-12 max(1, |value|).  scores against 
 max_leverage against the yardstick: 1e-6 (h = w g / sigma2 carries g's 1e-8 times w / sigma2, which stays below 1e2 in every case here).
 Every comparison prints one "LERR" line (error over its gate or scale) for the record.
 
-Size thresholds of asvgp_loo_1d's launch plan (csrc/loo.hip), each taken from both sides below:
+Size thresholds of asvgp_loo_1d's launch plan (csrc/row_scores.hip), each taken from both sides below:
   STAGE_MIN_N = 65 536   from here on the tables are staged in LDS, whole or split into ranges of mesh cells
   WRAP_N      = 262 144  the grid has at most this many threads (per range of cells), staged or not: beyond it the grid-stride loop wraps
   M = 1696 / 1697 (k = 4, D = 1)   the largest tables staged whole (8 (2 (k+1) (M + 1) + (M + 1) D + n_mesh + 64) bytes within

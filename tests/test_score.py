@@ -13,7 +13,7 @@ of the per-row outputs: 1e-12 of sum |terms|; counts exact.  Sums of a fold agai
   |d chi2|    <= (2 sum_d |r_d| / s2 + sum_d r_d^2 / s2^2) delta                    (chi2 = sq / s2, mean and s2 each move by delta)
 plus the 1e-12 sum |terms| of the summation itself.  Every comparison prints one "SERR" line (error over its gate or scale).
 
-Size thresholds of asvgp_score_1d's launch plan (csrc/score.hip), each taken from both sides below:
+Size thresholds of asvgp_score_1d's launch plan (csrc/row_scores.hip), each taken from both sides below:
   STAGE_MIN_N = 65 536   from here on the tables are staged in LDS, whole or split into ranges of mesh cells
   WRAP_N      = 262 144  the grid has at most this many threads (per range of cells): beyond it the grid-stride loop wraps
   M = 2907 / 2908 (k = 4, D = 1)   the largest tables staged whole (8 ((k+1) M + M D + n_mesh + 64) bytes within 160 KiB - 512) / the
