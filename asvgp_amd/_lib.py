@@ -68,6 +68,7 @@ SIGNATURES = {
     "asvgp_prior_forward_device": (_I, [_P, _P, _P, _P, _Z, _P]),
     "asvgp_prior_forward_stamps": (_I, [_P, _P, _P, _P, _P]),
     "asvgp_prior_plan_image_host": (_I, [_P, _I, _L, _I, _P, _P, _P, _P]),
+    "asvgp_elbo_launch_plan_host": (_I, [_I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "asvgp_elbo_grad_1d": (_I, [_P, _P, _P, _I, _D, _D, _D, _L, _L, _I, _L, _P, _P, _P, _Z, _P]),
     "asvgp_kuu_inverse_band_1d": (_I, [_P, _P, _I, _D, _D, _L, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_elbo_chain_sync": (_I, [_P, _I]),

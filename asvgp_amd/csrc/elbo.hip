@@ -9,9 +9,12 @@
 //   phase 1  factor   : block0 dual Cholesky(Kuu) (gpr.py:56) | block1 Cholesky(P) + c = L_P^-1 b (gpr.py:73-75)
 //   phase 2  inverse  : block0 dual Takahashi(Kuu) (gpr.py:59) | block1 Takahashi(P) + alpha = L_P^-T c
 //   phase 3  finalize : log-dets (gpr.py:57,74), band traces (gpr.py:60-70), 7-term bound (gpr.py:78-87), gradient
+#include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "bcr_pre.hpp"
 #include "bcr_mfma.hpp"
@@ -25,7 +28,8 @@ namespace asvgp {
 // 2 block cyclic reduction, both chains on the GPU, 3 block cyclic reduction with the PLANNED prior chain: forward pass of
 // the Kuu chain on the host in long double over the distinct nodes (prior_plan.cpp), backward pass on the GPU (bcr_pre.hpp),
 // 4 the planned chains on the matrix cores (bcr_mfma.hpp: k = 4, D = 1, M <= 2048).
-// Auto = 4 where it applies, else 3 when the handle holds a plan (asvgp_prior_plan_1d) for this (M, k, kind), else 2, else 1 (D > 1 or LDS).
+// Auto = 4 where it applies (and the entry point offers the fused finalize), else 3 when the handle holds a plan (asvgp_prior_plan_1d) for
+// this (M, k, kind) and the P chain fits the LDS, else 2 when both chains fit it (any D), else 1.  plan_chains below holds the rules.
 // With asvgp_elbo_chain_sync the prior chain (stream A) and the data chain (stream B) of algorithm 2 are ordered by the
 // handle's own events: evK = Kuu assembled (the P chain may start), evP = prior chain complete (the finalize may start).
 
@@ -83,6 +87,130 @@ template <int K> struct PostCovLauncher {
   static int run(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
                  double* alpha, double* W, double* Wd, int* info, void* ws, hipStream_t st);
 };
+
+// ---- The launch plan of the two chains: which kernels one call launches and in what shape, decided from integers alone BEFORE anything
+// happens.  plan_chains makes no HIP call, touches no handle and takes no table slot; the launchers below (one straight-line function per
+// path) execute a plan that was accepted, and asvgp_elbo_launch_plan_host shows the same function to the CPU tests.
+constexpr int FIN_LDS_DOUBLES = 16 * 14 + 2;          // LDS of the finalize reductions (elbo_finalize_body)
+constexpr size_t LDS_BYTES = 160 * 1024;
+enum ChainPath { PATH_SWEEPS = 0, PATH_BCR, PATH_BCR_PRIOR, PATH_BCR_DATA, PATH_PLANNED_BCR, PATH_PLANNED_MFMA };
+// who runs the forward pass of the planned Kuu chain: nobody (no planned chain) | this thread behind the launch | this thread in front of
+// it | the caller (asvgp_prior_publish) | the handle's worker thread | the GPU in double-double | asvgp_elbo_publish_theta (launch-ahead)
+enum ChainForward { FWD_NONE = 0, FWD_HOST_INLINE, FWD_HOST_BEFORE, FWD_DEFERRED, FWD_WORKER, FWD_GPU, FWD_AHEAD };
+struct ChainPlanIn {
+  int algo;                      // Handle::band_algo
+  bool have_plan; int n_rec;     // a prior plan for this (M, k, term count), and its record count
+  bool interior;                 // ... whose static bands have a Toeplitz interior (prior_plan_interior)
+  long M, D;
+  int part;                      // 0 whole, 1 prior half, 2 data half (the split entry points)
+  bool fused_fin;                // the caller offers a FusedFin
+  bool ahead_req, gpu_fwd, fwd_worker, defer_forward;   // Handle: ahead_req, prior_forward_gpu, fwd_worker, defer_forward
+  bool no_split, plan_first;     // debug_env()
+};
+struct ChainPlan {
+  int status; char msg[160];     // != ASVGP_OK: refused, nothing below counts
+  int path;                      // ChainPath
+  int part;                      // the effective part: 2 on a path without split scheduling runs as 0 ...
+  bool nothing;                  // ... and 1 there has nothing to do
+  bool big;                      // BIG layout of bcr.hpp: twice the nodes, couplings in an L2-resident plane - M up to 4096 at k = 4
+  size_t lds_bytes;              // dynamic LDS of the chains' kernel
+  int grid, n_helpers, split;    // workgroups of that kernel; of these, helpers that assemble Kuu; P chain on two workgroups
+  int fwd;                       // ChainForward
+  bool scale_alpha, scale_c;     // alpha / c are multiplied by 1 / s behind the chains (else the finalize applies it)
+};
+
+template <int K, bool TANGENT>
+static ChainPlan plan_chains(const ChainPlanIn& in) {
+  ChainPlan p{};
+  auto refuse = [&p](int status, const char* fmt, size_t bytes = 0) { p.status = status; snprintf(p.msg, sizeof(p.msg), fmt, bytes); return p; };
+  const int algo = in.algo;
+  const long M = in.M, nb = (M + K - 1) / K;
+  if ((algo == 3 || algo == 4) && !in.have_plan) return refuse(ASVGP_ERR_BAD_ARG, "band algorithms 3 and 4 need asvgp_prior_plan_1d for this (M, k, kernel)");
+  // the planned prior chain needs the LDS only for the P chain and the factor table
+  const bool planned0 = in.have_plan && (algo == 0 || algo == 3 || algo == 4);
+  const size_t ldsK = sizeof(double) * (TANGENT ? bcr_lds_doubles<Dual, K, 0>(nb) : bcr_lds_doubles<double, K, 0>(nb));
+  const size_t ldsP = sizeof(double) * bcr_lds_doubles<double, K, 1>(nb);
+  p.lds_bytes = planned0 ? ldsP : (ldsK > ldsP ? ldsK : ldsP);
+  bool fits = p.lds_bytes <= LDS_BYTES - 256;
+  constexpr bool HAS_BIG = (K <= 5);   // (the k = 6 BIG instantiation alone costs ~5 minutes of compile time)
+  if (HAS_BIG && !fits) {
+    const size_t bK = sizeof(double) * (TANGENT ? bcr_lds_doubles<Dual, K, 0, true>(nb) : bcr_lds_doubles<double, K, 0, true>(nb));
+    const size_t bP = sizeof(double) * bcr_lds_doubles<double, K, 1, true>(nb);
+    const size_t bb = planned0 ? bP : (bK > bP ? bK : bP);
+    if (bb <= LDS_BYTES - 256) { p.big = true; fits = true; p.lds_bytes = bb; }
+  }
+  const bool use_bcr = (algo == 2 || algo == 3 || algo == 4 || (algo == 0 && fits));   // (D > 1: column 0 rides through the levels, the others replay the factors)
+  const bool planned = planned0 && use_bcr;
+  p.part = in.part;
+  if (in.part != 0 && (!use_bcr || planned)) {
+    // split scheduling exists for the all-GPU BCR path only: the sweeps and the planned chain run as one unit in the data call
+    if (in.part == 1) { p.nothing = true; return p; }
+    p.part = 0;
+  }
+  p.scale_alpha = !TANGENT;            // (the ELBO launchers leave alpha unscaled and let the finalize apply 1 / s)
+  const char* ahead_only = "launch-ahead exists for the matrix-core launch only (k = 4, D = 1, M <= 2048, planned prior chain)";
+  if (planned) {
+    // matrix-core chains: k = 4, one output column, the whole tree in one workgroup's LDS, a Toeplitz interior for the closed-form Kuu
+    bool mfma = false;
+    size_t lds_mfma = 0;
+    if constexpr (K == BM_B) {
+      const size_t lb = sizeof(double) * bcr_mfma_lds_doubles(nb), lk = sizeof(double) * bcr_mfma_pre_lds_doubles(nb, in.n_rec);
+      mfma = (algo == 0 || algo == 4) && in.D == 1 && nb <= 512 && TANGENT && in.fused_fin && lb <= LDS_BYTES && lk <= LDS_BYTES && in.interior;
+      lds_mfma = lb > lk ? lb : lk;
+    }
+    if (algo == 4 && !mfma)
+      return refuse(ASVGP_ERR_UNSUPPORTED, "band algorithm 4 (matrix-core chains) needs k = 4, D = 1, M <= 2048, Toeplitz static bands and the ELBO + gradient entry point");
+    if (in.ahead_req && !mfma) return refuse(ASVGP_ERR_UNSUPPORTED, ahead_only);
+    if (!mfma) {
+      if (!fits) return refuse(ASVGP_ERR_LDS_CAPACITY, "BCR needs %zu B of LDS", p.lds_bytes);
+      p.path = PATH_PLANNED_BCR;
+      const size_t lds_pre = sizeof(double) * bcr_pre_lds_doubles(K, in.n_rec);
+      if (lds_pre > p.lds_bytes) p.lds_bytes = lds_pre;
+      // 2 + 6 = 8 workgroups: one per XCD (workgroups are dealt to the XCDs round-robin).  Every workgroup of the launch reserves the
+      // chains' ~100 KB of LDS, i.e. a CU of its own; with 10 workgroups two of them shared an XCD, and the second ELBO launch of the
+      // in-flight schedule found no free CU there for a helper - its P chain then waited for the whole previous launch to finish
+      p.n_helpers = (int)((M + 255) / 256 < 6 ? (M + 255) / 256 : 6);
+      p.grid = 2 + p.n_helpers;
+      p.fwd = in.gpu_fwd ? FWD_GPU : FWD_HOST_BEFORE;
+      return p;
+    }
+    if (in.ahead_req && (in.gpu_fwd || in.plan_first)) return refuse(ASVGP_ERR_UNSUPPORTED, "launch-ahead needs the host forward pass (asvgp_set_prior_forward(h, 0))");
+    p.path = PATH_PLANNED_MFMA;
+    p.big = false;
+    p.lds_bytes = lds_mfma > sizeof(double) * FIN_LDS_DOUBLES ? lds_mfma : sizeof(double) * FIN_LDS_DOUBLES;
+    // the P chain on two workgroups where its wide levels are throughput-bound (bcr_mfma.hpp BmSplit); no helpers: both chains form
+    // Kuu / dKuu in closed form, nobody assembles the bands
+    p.split = (nb >= 128 && !in.no_split) ? 1 : 0;
+    p.grid = 2 + p.split;
+    p.fwd = in.ahead_req ? FWD_AHEAD : in.gpu_fwd ? FWD_GPU : in.plan_first ? FWD_HOST_BEFORE : in.fwd_worker ? FWD_WORKER
+          : in.defer_forward ? FWD_DEFERRED : FWD_HOST_INLINE;
+    return p;
+  }
+  if (in.ahead_req) return refuse(ASVGP_ERR_UNSUPPORTED, ahead_only);
+  if (!use_bcr) {                      // sequential sweeps: c = L_P^-1 b / s (gpr.py:75), alpha = P^-1 b / s
+    p.path = PATH_SWEEPS; p.big = false; p.lds_bytes = 0; p.grid = 2; p.scale_alpha = p.scale_c = true;
+    return p;
+  }
+  if (!fits) return refuse(ASVGP_ERR_LDS_CAPACITY, "BCR forced but needs %zu B of LDS", p.lds_bytes);
+  p.path = p.part == 1 ? PATH_BCR_PRIOR : (p.part == 2 ? PATH_BCR_DATA : PATH_BCR);
+  p.grid = p.part == 0 ? 2 : 1;
+  if (p.part == 1) p.scale_alpha = false;
+  return p;
+}
+
+// one case per built bandwidth: f(std::integral_constant<int, k>)
+template <class F>
+static int for_bandwidth(int k, F&& f) {
+  switch (k) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+  }
+  return ASVGP_ERR_UNSUPPORTED;
+}
 
 #ifdef ASVGP_ELBO_ONLY_K
 struct KuuCoefs2 { double c[ASVGP_MAX_KUU_TERMS]; double dc[ASVGP_MAX_KUU_TERMS]; int n; };
@@ -374,8 +502,6 @@ __device__ __forceinline__ void elbo_finalize_body(
   }
 #undef is_last
 }
-
-constexpr int FIN_LDS_DOUBLES = 16 * 14 + 2;
 
 template <int KT>
 __global__ __launch_bounds__(256) void elbo_finalize_kernel(
@@ -807,265 +933,271 @@ static __global__ void scale_kernel(double* __restrict__ x, double f, long n) {
   if (i < n) x[i] = x[i] * f;
 }
 
+static double now_us() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
+
+// what every launcher of a plan needs of the call
+struct ChainCall {
+  Handle* h; const double *S, *A, *b; KuuCoefs2 cf; int kind; double s; long M, D; Ws w; int* info; hipStream_t st; const FusedFin* fin;
+  double t_enter;                                            // ASVGP_HOST_TIMES: when run_chains was entered
+};
+static void scale_after(const ChainCall& c, const ChainPlan& p) {
+  const long n = c.M * c.D;
+  if (p.scale_c) hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, c.w.c, 1.0 / c.s, n);
+  if (p.scale_alpha) hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, c.w.alpha, 1.0 / c.s, n);
+}
+static void set_pending_forward(Handle* h, const KuuCoefs2& cf, const TableSlot& slot) {
+  for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) { h->fwd.coef[t] = cf.c[t]; h->fwd.dcoef[t] = cf.dc[t]; }
+  h->fwd.tab = slot.tab; h->fwd.slot = slot.slot; h->fwd.seq = slot.seq;
+}
+// the fused finalize of the planned launches as this plan shapes it (finalize = 1 when the caller offered one)
+static FusedFin chain_fin(const ChainCall& c, const ChainPlan& p) {
+  FusedFin ff{};
+  if (c.fin) { ff = *c.fin; ff.finalize = 1; }
+  ff.n_helpers = p.n_helpers;
+  ff.split = p.split;
+  ff.xchg = p.split ? c.w.LP : nullptr;                     // (the sequential sweeps' factor band: unused by the matrix-core launch)
+  ff.assembled = reinterpret_cast<unsigned*>(c.w.fin + 20);
+  ff.debug_no_assembly = debug_env().no_assembly;           // test hook: the helpers never report -> the P chain gives up waiting
+  ff.debug_stamps = debug_env().chain_stamps;
+  return ff;
+}
+// dKuu / dl in closed form for the matrix-core P chain's own traces: interior values, boundary table as KuuInterior / ThetaBox carry it
+static void interior_dkuu(const PriorPlan* plan, const double* dc, double* dk, double* dkb) {
+  double bnd2[2 * PRIOR_BND_DIAGS * PRIOR_BND];
+  long lo2 = 0, hi2 = 0;
+  prior_plan_interior_kuu(plan, dc, dk, &lo2, &hi2, bnd2);
+  for (int sd = 0; sd < 2; ++sd)
+    for (int d = 0; d <= BM_B; ++d)
+      for (int cI = 0; cI < KI_DKB; ++cI)
+        dkb[(sd * 5 + d) * KI_DKB + cI] = bnd2[(size_t)(sd * PRIOR_BND_DIAGS + d) * PRIOR_BND + cI];
+}
+static int grant_lds(const void* kern, size_t lds_bytes) {
+  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (e == hipSuccess) return ASVGP_OK;
+  set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
+  return ASVGP_ERR_LDS_CAPACITY;
+}
+
+// ---- planned prior chain, both chains on the matrix cores.  The order of events is what the dependent step's time rests on: the launch
+// goes out FIRST - its ~8 us of dispatch latency and the P chain (which needs only Kuu, not its factors) run while this thread, the worker
+// or the caller does the forward pass -, then the forward pass, then the ready word the Kuu workgroup waits on (bcr_mfma_backward_pre).
+template <int K>
+static int launch_planned_mfma(const ChainCall& c, const ChainPlan& p) {
+  Handle* h = c.h;
+  const Ws& w = c.w;
+  const int n_rec = prior_plan_nrec(h->plan);
+  const bool host_times = debug_env().host_times != 0;      // (measurement aid: where this call's host time goes)
+  KuuInterior ki;
+  prior_plan_interior_kuu(h->plan, c.cf.c, ki.k, &ki.lo, &ki.hi, ki.bnd);   // Kuu in closed form for the P chain's level-0 loads
+  interior_dkuu(h->plan, c.cf.dc, ki.dk, ki.dkb);
+  ki.dk_tab = (ki.lo <= KI_DKB && c.M - ki.hi <= KI_DKB) ? 1 : 0;
+  const double t_acq0 = host_times ? now_us() : 0.0;
+  TableSlot slot(h);
+  const double t_acq1 = host_times ? now_us() : 0.0;
+  const double* tab_k = h->tab_dev + (size_t)slot.slot * h->slot_doubles;
+  const unsigned long long* ready = h->ready_dev + slot.slot;
+  if (p.fwd == FWD_GPU) {
+    // asvgp_set_prior_forward(h, 1): the pass in double-double (prior_dd.hip) on the handle's own stream BESIDE this launch, whose Kuu
+    // workgroup waits for the pass's ready word as it does for the host's; the table then sits in the handle's device ring
+    double* t = nullptr;
+    const int rc = handle_prior_dd_forward(h, c.cf.c, c.cf.dc, slot.slot, c.st, &t, nullptr, slot.seq, &ready);
+    if (rc) return rc;
+    tab_k = t;
+  }
+  FusedFin ff = chain_fin(c, p);
+  const long spin_limit = debug_env().spin_limit;
+  auto kern = elbo_chains_mfma_kernel<K>;
+  static size_t lds_granted[16] = {0};                      // per device: the dynamic-LDS size already granted to this kernel
+  size_t& granted = lds_granted[h->device & 15];
+  if (p.lds_bytes > granted) {
+    const int rc = grant_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+    if (rc) return rc;
+    granted = p.lds_bytes;
+  }
+  const double t0 = host_times ? now_us() : 0.0;
+  const ThetaBox* box_k = nullptr;
+  if (p.fwd == FWD_HOST_BEFORE) {                           // (ASVGP_PLAN_FIRST, measurement aid: forward pass, then launch; nobody waits)
+    (void)prior_plan_eval(h->plan, c.cf.c, c.cf.dc, slot.tab);
+    ready = nullptr;
+  } else if (p.fwd == FWD_AHEAD) {
+    // launch-ahead: theta comes later, through the handle's pinned box ring (asvgp_elbo_publish_theta), and so does the forward pass
+    static_assert(sizeof(ThetaBox) <= BOX_BYTES, "theta box");
+    if (!h->box_host) {
+      if (hipHostMalloc(&h->box_host, BOX_BYTES * TAB_SLOTS, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess ||
+          hipHostGetDevicePointer(&h->box_dev, h->box_host, 0) != hipSuccess) {
+        if (h->box_host) { (void)hipHostFree(h->box_host); h->box_host = nullptr; }
+        set_error("launch-ahead: pinned allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return ASVGP_ERR_HIP;
+      }
+      memset(h->box_host, 0, BOX_BYTES * TAB_SLOTS);
+    }
+    ThetaBox* bh = reinterpret_cast<ThetaBox*>(static_cast<char*>(h->box_host) + (size_t)slot.slot * BOX_BYTES);
+    __atomic_store_n(&bh->seq, 0ull, __ATOMIC_RELEASE);     // (not this launch's theta yet)
+    box_k = reinterpret_cast<const ThetaBox*>(static_cast<const char*>(h->box_dev) + (size_t)slot.slot * BOX_BYTES);
+  }
+  if (h->mirror_dev) { ff.mirror = h->mirror_dev; ff.mirror_seq = ++h->mirror_seq; h->mirror_pending = ff.mirror_seq; }
+  if (p.fwd == FWD_WORKER) {                                // the handle's worker thread starts on the table NOW, beside the launch call
+    set_pending_forward(h, c.cf, slot);
+    handle_post_forward(h);
+  }
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BM_THREADS), p.lds_bytes, c.st, ki, c.S, c.cf, w.Kuu, w.dK, c.A, c.b, (int)c.M, w.bcrP, w.SP, w.alpha,
+                     w.logdets, c.info, c.s, tab_k, n_rec, h->node_rec_dev, w.bcrK, w.SK, w.dSK, h->done_dev + slot.slot, slot.seq, ready, spin_limit, ff,
+                     box_k);
+  switch (p.fwd) {
+    case FWD_AHEAD: {
+      const int rc = slot.launched(check_launch("elbo chains (matrix cores, launched ahead of theta)"));
+      if (rc == ASVGP_OK) h->ahead = Handle::PendingAhead{true, slot.slot, slot.seq, slot.tab, c.kind, ff.th.N, ff.th.Nw, ff.th.cw};
+      return rc;
+    }
+    case FWD_GPU: return slot.launched(check_launch("elbo chains (matrix cores, forward pass on the GPU)"));
+    case FWD_WORKER: return slot.launched(check_launch("elbo chains (matrix cores, forward pass on the worker thread)"));
+    case FWD_DEFERRED:                                      // the caller runs the forward pass later (asvgp_prior_publish): e.g. after
+      h->fwd.valid = true;                                  // enqueueing other work that should not wait 19 us behind it
+      set_pending_forward(h, c.cf, slot);
+      return slot.launched(check_launch("elbo chains (matrix cores, forward pass deferred)"));
+    default: break;
+  }
+  const double t1 = host_times ? now_us() : 0.0;
+  if (p.fwd == FWD_HOST_INLINE) (void)prior_plan_eval(h->plan, c.cf.c, c.cf.dc, slot.tab);   // a non-positive pivot is reported through `info` by the kernel
+  if (host_times) {
+    static double acc_launch = 0.0, acc_plan = 0.0, acc_pre = 0.0, acc_acq = 0.0, acc_a = 0.0;
+    static long calls = 0;
+    const bool plan_first = p.fwd == FWD_HOST_BEFORE;
+    const double t2 = now_us();
+    acc_acq += t_acq1 - t_acq0; acc_a += t_acq0 - c.t_enter;
+    acc_pre += t0 - c.t_enter; acc_launch += t1 - t0; acc_plan += t2 - t1;
+    if (++calls % 200 == 0) {
+      fprintf(stderr, "[entry -> acquire %.1f us, table acquire %.1f us] ", acc_a / 200, acc_acq / 200);
+      fprintf(stderr, "[asvgp host times, mean of 200 calls] entry -> launch call %.1f us | launch call (%s) %.1f us | %s %.1f us\n", acc_pre / 200,
+              plan_first ? "forward pass + hipLaunchKernel" : "hipLaunchKernel", acc_launch / 200, plan_first ? "-" : "forward pass", acc_plan / 200);
+      acc_a = acc_acq = acc_launch = acc_plan = acc_pre = 0.0;
+    }
+  }
+  __atomic_store_n(h->ready_host + slot.slot, slot.seq, __ATOMIC_RELEASE);
+  return slot.launched(check_launch("elbo chains (planned prior)"));
+}
+
+// ---- planned prior chain on the BCR kernel: the forward pass (host, ~20 us, or GPU) in front of the launch.  Kuu / dKuu (finalize
+// traces, P = A/s + Kuu in the P chain's gathers) are assembled by the launch's helper workgroups.
+template <int K, bool TANGENT>
+static int launch_planned_bcr(const ChainCall& c, const ChainPlan& p) {
+  Handle* h = c.h;
+  const Ws& w = c.w;
+  constexpr bool HAS_BIG = (K <= 5);
+  const int n_rec = prior_plan_nrec(h->plan);
+  TableSlot slot(h);
+  const double* tab_k = h->tab_dev + (size_t)slot.slot * h->slot_doubles;
+  if (p.fwd == FWD_GPU) {              // asvgp_set_prior_forward(h, 1): in front of the chains on the same stream; no launch waits for the host
+    double* t = nullptr;
+    const int rc = handle_prior_dd_forward(h, c.cf.c, c.cf.dc, slot.slot, c.st, &t);
+    if (rc) return rc;
+    tab_k = t;
+  } else {
+    (void)prior_plan_eval(h->plan, c.cf.c, c.cf.dc, slot.tab);   // a non-positive pivot is reported through `info` by the kernel
+    __atomic_store_n(h->ready_host + slot.slot, slot.seq, __ATOMIC_RELEASE);
+  }
+  const FusedFin ff = chain_fin(c, p);
+  auto kern = p.big ? elbo_chains_kernel<K, HAS_BIG> : elbo_chains_kernel<K, false>;
+  const int rc = grant_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BCR_THREADS), p.lds_bytes, c.st, c.S, c.cf, w.Kuu, TANGENT ? w.dK : (double*)nullptr, c.A, c.b,
+                     (int)c.M, w.bcrP, w.SP, w.alpha, w.logdets, c.info, c.s, tab_k, n_rec, h->node_rec_dev, w.bcrK, w.SK, w.dSK,
+                     h->done_dev + slot.slot, slot.seq, (int)c.D, (int)(p.lds_bytes / sizeof(double)), ff);
+  scale_after(c, p);
+  return slot.launched(check_launch("elbo chains (planned prior)"));
+}
+
+// ---- block cyclic reduction, both chains on the GPU: whole, or as the halves of the split entry points.  Kuu / dKuu (theta only) are
+// written by the prior half, P = A/s + Kuu is formed by the data half inside its gathers (it re-forms Kuu in registers).
+template <int K, bool TANGENT>
+static int launch_bcr(const ChainCall& c, const ChainPlan& p) {
+  const Ws& w = c.w;
+  constexpr bool HAS_BIG = (K <= 5);
+  const long E = (long)(K + 1) * c.M;
+  hipLaunchKernelGGL(elbo_prepare_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c.st, c.S, c.cf, E, c.A, c.s, w.Kuu, w.dK, w.P);
+  auto kern = p.big ? elbo_bcr_kernel<K, TANGENT, HAS_BIG> : elbo_bcr_kernel<K, TANGENT, false>;
+  const int rc = grant_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BCR_THREADS), p.lds_bytes, c.st, w.Kuu, w.dK, w.P, c.b, (int)c.M, w.bcrK, w.bcrP, w.SK, w.dSK, w.SP,
+                     w.alpha, w.logdets, c.info, debug_env().bcr_stamps, 0, (int)c.D, (int)(p.lds_bytes / sizeof(double)));
+  scale_after(c, p);
+  return check_launch("elbo chains");
+}
+template <int K>
+static int launch_bcr_prior(const ChainCall& c, const ChainPlan& p) {
+  Handle* h = c.h;
+  const Ws& w = c.w;
+  constexpr bool HAS_BIG = (K <= 5);
+  const long E = (long)(K + 1) * c.M;
+  hipLaunchKernelGGL(elbo_prepare_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c.st, c.S, c.cf, E, c.A, c.s, w.Kuu, w.dK, (double*)nullptr);
+  if (h->sync_on) (void)hipEventRecord(h->evK, c.st);
+  auto kern = p.big ? elbo_bcr_prior_kernel<K, HAS_BIG> : elbo_bcr_prior_kernel<K, false>;
+  const int rc = grant_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BCR_THREADS), p.lds_bytes, c.st, w.Kuu, w.dK, (int)c.M, w.bcrK, w.SK, w.dSK, w.logdets, c.info,
+                     debug_env().bcr_stamps);
+  if (h->sync_on) (void)hipEventRecord(h->evP, c.st);
+  return check_launch("elbo prior chain");
+}
+template <int K>
+static int launch_bcr_data(const ChainCall& c, const ChainPlan& p) {
+  Handle* h = c.h;
+  const Ws& w = c.w;
+  constexpr bool HAS_BIG = (K <= 5);
+  if (h->sync_on) (void)hipStreamWaitEvent(c.st, h->evK, 0);
+  auto kern = p.big ? elbo_bcr_data_kernel<K, HAS_BIG> : elbo_bcr_data_kernel<K, false>;
+  const int rc = grant_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(BCR_THREADS), p.lds_bytes, c.st, w.Kuu, c.A, c.b, (int)c.M, w.bcrP, w.SP, w.alpha, w.logdets, c.info,
+                     debug_env().bcr_stamps, c.s, (int)c.D, (int)(p.lds_bytes / sizeof(double)));
+  scale_after(c, p);
+  return check_launch("elbo chains");
+}
+
+// ---- sequential single-wave sweeps (the reference's elimination order): two kernels for one output column, four for more
+template <int K, bool TANGENT>
+static int launch_sweeps(const ChainCall& c, const ChainPlan& p) {
+  const Ws& w = c.w;
+  const long E = (long)(K + 1) * c.M, D = c.D;
+  const int M = (int)c.M;
+  hipLaunchKernelGGL(elbo_prepare_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c.st, c.S, c.cf, E, c.A, c.s, w.Kuu, w.dK, w.P);
+  if (D == 1) {
+    hipLaunchKernelGGL((elbo_factor_kernel<K, TANGENT, true>), dim3(p.grid), dim3(64), 0, c.st, w.Kuu, w.dK, w.P, w.LK, w.dLK, w.LP, c.b, w.c, M, c.info);
+    hipLaunchKernelGGL((elbo_inverse_kernel<K, TANGENT, true>), dim3(p.grid), dim3(64), 0, c.st, w.LK, w.dLK, w.LP, w.SK, w.dSK, w.SP, w.c, w.alpha, M);
+  } else {
+    hipLaunchKernelGGL((elbo_factor_kernel<K, TANGENT, false>), dim3(p.grid), dim3(64), 0, c.st, w.Kuu, w.dK, w.P, w.LK, w.dLK, w.LP, c.b, w.c, M, c.info);
+    hipLaunchKernelGGL(elbo_trsv_kernel<K>, dim3((unsigned)D), dim3(64), 0, c.st, w.LP, M, c.b, w.c, D, 0, 1.0);
+    hipLaunchKernelGGL((elbo_inverse_kernel<K, TANGENT, false>), dim3(p.grid), dim3(64), 0, c.st, w.LK, w.dLK, w.LP, w.SK, w.dSK, w.SP, w.c, w.alpha, M);
+    hipLaunchKernelGGL(elbo_trsv_kernel<K>, dim3((unsigned)D), dim3(64), 0, c.st, w.LP, M, w.c, w.alpha, D, 1, 1.0);
+  }
+  scale_after(c, p);
+  return check_launch("elbo chains");
+}
+
+// coefficients -> plan -> refuse or dispatch.  `p` tells the caller which path ran (a fused finalize rode along on the planned ones).
 template <int K, bool TANGENT>
 static int run_chains(Handle* h, const double* stats, const double* S, int kind, double v, double l, double s, long M, long D,
-                      Ws w, int* info, hipStream_t st, bool& use_bcr, int part = 0, bool scale_alpha = true, FusedFin* fin = nullptr) {
-  double t_enter = 0.0;
-  if (debug_env().host_times) { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); t_enter = ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
-  KuuCoefs2 cf;
-  for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) cf.c[t] = cf.dc[t] = 0.0;
-  int rc = asvgp_matern_coeffs(kind, v, l, cf.c, cf.dc, &cf.n);
+                      Ws w, int* info, hipStream_t st, ChainPlan& p, int part = 0, const FusedFin* fin = nullptr) {
+  ChainCall c{h, S, stats, stats ? stats + (long)(K + 1) * M : nullptr, {}, kind, s, M, D, w, info, st, fin, debug_env().host_times ? now_us() : 0.0};
+  for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) c.cf.c[t] = c.cf.dc[t] = 0.0;
+  const int rc = asvgp_matern_coeffs(kind, v, l, c.cf.c, c.cf.dc, &c.cf.n);
   if (rc) return rc;
-  const long E = (long)(K + 1) * M;
-  const double* A = stats;
-  const double* b = stats ? stats + E : nullptr;
-  const long nb = (M + K - 1) / K;
-  const int algo = h->band_algo;
-  // the planned prior chain needs the LDS only for the P chain and the factor table
-  const bool have_plan = h->plan && prior_plan_M(h->plan) == M && prior_plan_k(h->plan) == K && prior_plan_terms(h->plan) == cf.n;
-  if ((algo == 3 || algo == 4) && !have_plan) { set_error("band algorithms 3 and 4 need asvgp_prior_plan_1d for this (M, k, kernel)"); return ASVGP_ERR_BAD_ARG; }
-  size_t ldsK = sizeof(double) * (TANGENT ? bcr_lds_doubles<Dual, K, 0>(nb) : bcr_lds_doubles<double, K, 0>(nb));
-  size_t ldsP = sizeof(double) * bcr_lds_doubles<double, K, 1>(nb);
-  bool planned = have_plan && (algo == 0 || algo == 3 || algo == 4);
-  size_t lds_bytes = planned ? ldsP : (ldsK > ldsP ? ldsK : ldsP);
-  bool fits = lds_bytes <= 160 * 1024 - 256;
-  bool big = false;   // BIG layout (bcr.hpp): twice the nodes, couplings in an L2-resident plane - M up to 4096 at k = 4
-  constexpr bool HAS_BIG = (K <= 5);   // (the k = 6 BIG instantiation alone costs ~5 minutes of compile time)
-  if (HAS_BIG && !fits) {
-    size_t bK = sizeof(double) * (TANGENT ? bcr_lds_doubles<Dual, K, 0, true>(nb) : bcr_lds_doubles<double, K, 0, true>(nb));
-    size_t bP = sizeof(double) * bcr_lds_doubles<double, K, 1, true>(nb);
-    size_t bb = planned ? bP : (bK > bP ? bK : bP);
-    if (bb <= 160 * 1024 - 256) { big = true; fits = true; lds_bytes = bb; }
+  const bool have_plan = h->plan && prior_plan_M(h->plan) == M && prior_plan_k(h->plan) == K && prior_plan_terms(h->plan) == c.cf.n;
+  p = plan_chains<K, TANGENT>(ChainPlanIn{h->band_algo, have_plan, have_plan ? prior_plan_nrec(h->plan) : 0, have_plan && prior_plan_interior(h->plan),
+                                          M, D, part, fin != nullptr, h->ahead_req, h->prior_forward_gpu, h->fwd_worker, h->defer_forward,
+                                          debug_env().no_split != 0, debug_env().plan_first != 0});
+  if (p.status) { set_error("%s", p.msg); return p.status; }
+  if (p.nothing) return ASVGP_OK;
+  switch (p.path) {
+    case PATH_PLANNED_MFMA: if constexpr (K == BM_B) return launch_planned_mfma<K>(c, p); break;
+    case PATH_PLANNED_BCR: return launch_planned_bcr<K, TANGENT>(c, p);
+    case PATH_BCR: return launch_bcr<K, TANGENT>(c, p);
+    case PATH_BCR_PRIOR: if constexpr (TANGENT) return launch_bcr_prior<K>(c, p); break;
+    case PATH_BCR_DATA: return launch_bcr_data<K>(c, p);
+    case PATH_SWEEPS: return launch_sweeps<K, TANGENT>(c, p);
   }
-  use_bcr = (algo == 2 || algo == 3 || algo == 4 || (algo == 0 && fits));   // (D > 1: column 0 rides through the levels, the others replay the factors)
-  planned = planned && use_bcr;
-  if (part != 0 && (!use_bcr || planned)) {
-    // split scheduling exists for the all-GPU BCR path only: the sweeps and the planned chain run as one unit in the data call
-    if (part == 1) return ASVGP_OK;
-    part = 0;
-  }
-  if (planned) {
-    // ---- host: forward pass of the Kuu chain for this theta (prior_plan.cpp, ~20 us) into the next slot of the pinned ring.
-    // Kuu / dKuu (finalize traces, P = A/s + Kuu in the P chain's gathers) are assembled by the chain workgroups themselves.
-    // matrix-core chains: k = 4, one output column, the whole tree in one workgroup's LDS, a Toeplitz interior for the closed-form Kuu;
-    // decided BEFORE a table slot is taken (a refused call must not leave a slot whose kernel never reports)
-    const int n_rec = prior_plan_nrec(h->plan);
-    bool use_mfma = false;
-    KuuInterior ki;
-    if constexpr (K == BM_B) {
-      use_mfma = (algo == 0 || algo == 4) && D == 1 && nb <= 512 && TANGENT && fin != nullptr &&
-                 sizeof(double) * bcr_mfma_lds_doubles(nb) <= 160 * 1024 && sizeof(double) * bcr_mfma_pre_lds_doubles(nb, n_rec) <= 160 * 1024;
-      if (use_mfma) {
-        prior_plan_interior_kuu(h->plan, cf.c, ki.k, &ki.lo, &ki.hi, ki.bnd);   // Kuu in closed form for the P chain's level-0 loads
-        use_mfma = ki.hi > ki.lo;                                                // (none: the older kernel, which waits for the assembled band)
-        if (use_mfma) {                                                          // dKuu / dl on the interior, for the P chain's own traces
-          double bnd2[2 * PRIOR_BND_DIAGS * PRIOR_BND];
-          long lo2 = 0, hi2 = 0;
-          prior_plan_interior_kuu(h->plan, cf.dc, ki.dk, &lo2, &hi2, bnd2);
-          ki.dk_tab = (ki.lo <= KI_DKB && M - ki.hi <= KI_DKB) ? 1 : 0;
-          for (int sd = 0; sd < 2; ++sd)
-            for (int d = 0; d <= K; ++d)
-              for (int cI = 0; cI < KI_DKB; ++cI)
-                ki.dkb[(sd * 5 + d) * KI_DKB + cI] = bnd2[(size_t)(sd * PRIOR_BND_DIAGS + d) * PRIOR_BND + cI];
-        }
-      }
-    }
-    if (algo == 4 && !use_mfma) {
-      set_error("band algorithm 4 (matrix-core chains) needs k = 4, D = 1, M <= 2048, Toeplitz static bands and the ELBO + gradient entry point");
-      return ASVGP_ERR_UNSUPPORTED;
-    }
-    if (h->ahead_req && !use_mfma) { set_error("launch-ahead exists for the matrix-core launch only (k = 4, D = 1, M <= 2048, planned prior chain)"); return ASVGP_ERR_UNSUPPORTED; }
-    if (!use_mfma && !fits) { set_error("BCR needs %zu B of LDS", lds_bytes); return ASVGP_ERR_LDS_CAPACITY; }
-    unsigned long long seq = 0;
-    int slot = 0;
-    double t_acq0 = 0.0, t_acq1 = 0.0;
-    if (debug_env().host_times) { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); t_acq0 = ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
-    double* tab = handle_table_acquire(h, &seq, &slot);
-    if (debug_env().host_times) { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); t_acq1 = ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
-    // asvgp_set_prior_forward(h, 1): the forward pass runs on the GPU in double-double (prior_dd.hip), enqueued here in front of the
-    // chains' launch; the table then sits in the handle's device ring and no launch waits for the host
-    const bool gpu_fwd = h->prior_forward_gpu;
-    const double* tab_k = h->tab_dev + (size_t)slot * h->slot_doubles;
-    const unsigned long long* dd_ready = nullptr;
-    if (gpu_fwd) {
-      // the matrix-core launch: the pass on the handle's own stream BESIDE the chains' launch (its Kuu workgroup waits for the ready word as
-      // it does for the host's - the P chain does not wait at all); the other launches: in front, on the same stream
-      double* t = nullptr;
-      rc = handle_prior_dd_forward(h, cf.c, cf.dc, slot, st, &t, nullptr, use_mfma ? seq : 0ull, use_mfma ? &dd_ready : nullptr);
-      if (rc) return rc;
-      tab_k = t;
-    }
-    size_t lds_pre = sizeof(double) * bcr_pre_lds_doubles(K, n_rec);
-    if (lds_pre > lds_bytes) lds_bytes = lds_pre;
-    FusedFin ff{};
-    if (fin) { ff = *fin; ff.finalize = 1; fin->finalize = -1; }   // (-1: tells the caller that the finalize rode along)
-    // 2 + 6 = 8 workgroups: one per XCD (workgroups are dealt to the XCDs round-robin).  Every workgroup of the launch reserves the
-    // chains' ~100 KB of LDS, i.e. a CU of its own; with 10 workgroups two of them shared an XCD, and the second ELBO launch of the
-    // in-flight schedule found no free CU there for a helper - its P chain then waited for the whole previous launch to finish
-    ff.n_helpers = (int)((M + 255) / 256 < 6 ? (M + 255) / 256 : 6);
-    ff.split = 0; ff.xchg = nullptr;
-    ff.assembled = reinterpret_cast<unsigned*>(w.fin + 20);
-    ff.debug_no_assembly = debug_env().no_assembly;
-    ff.debug_stamps = debug_env().chain_stamps;   // test hook: the helpers never report -> the P chain gives up waiting
-    const long spin_limit = debug_env().spin_limit;
-    if constexpr (K == BM_B) {
-      if (use_mfma) {
-        size_t lb = sizeof(double) * bcr_mfma_lds_doubles(nb), lk = sizeof(double) * bcr_mfma_pre_lds_doubles(nb, n_rec);
-        if (lk > lb) lb = lk;
-        if (sizeof(double) * FIN_LDS_DOUBLES > lb) lb = sizeof(double) * FIN_LDS_DOUBLES;
-        auto kern = elbo_chains_mfma_kernel<K>;
-        static size_t lds_granted[16] = {0};                     // per device: the dynamic-LDS size already granted to this kernel
-        size_t& granted = lds_granted[h->device & 15];
-        if (lb > granted) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-          if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-          granted = lb;
-        }
-        if (h->mirror_dev) { ff.mirror = h->mirror_dev; ff.mirror_seq = ++h->mirror_seq; h->mirror_pending = ff.mirror_seq; }
-        // the P chain on two workgroups where its wide levels are throughput-bound (bcr_mfma.hpp BmSplit); 8 workgroups in all, one per XCD
-        if (nb >= 128 && !debug_env().no_split) {
-          ff.split = 1;
-          ff.xchg = w.LP;                                      // (the sequential sweeps' factor band: unused by this launch)
-        }
-        ff.n_helpers = 0;                                       // (both chains form Kuu / dKuu in closed form: nobody assembles the bands here)
-        // The launch goes out FIRST: its ~8 us of dispatch latency, the helpers' assembly and the P chain (which needs only Kuu, not its
-        // factors) run while this thread does the forward pass below; the Kuu workgroup waits on ready[slot] (bcr_mfma_backward_pre).
-        const bool plan_first = debug_env().plan_first != 0;   // (measurement aid: the round-2 order, forward pass then launch)
-        const bool host_times = debug_env().host_times != 0;   // (measurement aid: where this call's host time goes)
-        auto now_us = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
-        const double t0 = host_times ? now_us() : 0.0;
-        if (plan_first && !gpu_fwd) (void)prior_plan_eval(h->plan, cf.c, cf.dc, tab);
-        // launch-ahead: theta comes later, through the handle's pinned box ring (asvgp_elbo_publish_theta); nothing below runs the forward pass
-        const ThetaBox* box_k = nullptr;
-        if (h->ahead_req) {
-          if (gpu_fwd || plan_first) { set_error("launch-ahead needs the host forward pass (asvgp_set_prior_forward(h, 0))"); return ASVGP_ERR_UNSUPPORTED; }
-          static_assert(sizeof(ThetaBox) <= BOX_BYTES, "theta box");
-          if (!h->box_host) {
-            if (hipHostMalloc(&h->box_host, BOX_BYTES * TAB_SLOTS, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess ||
-                hipHostGetDevicePointer(&h->box_dev, h->box_host, 0) != hipSuccess) {
-              if (h->box_host) { (void)hipHostFree(h->box_host); h->box_host = nullptr; }
-              set_error("launch-ahead: pinned allocation failed: %s", hipGetErrorString(hipGetLastError()));
-              return ASVGP_ERR_HIP;
-            }
-            memset(h->box_host, 0, BOX_BYTES * TAB_SLOTS);
-          }
-          ThetaBox* bh = reinterpret_cast<ThetaBox*>(static_cast<char*>(h->box_host) + (size_t)slot * BOX_BYTES);
-          __atomic_store_n(&bh->seq, 0ull, __ATOMIC_RELEASE);     // (not this launch's theta yet)
-          box_k = reinterpret_cast<const ThetaBox*>(static_cast<const char*>(h->box_dev) + (size_t)slot * BOX_BYTES);
-        }
-        const bool to_worker = !plan_first && !gpu_fwd && h->fwd_worker && !h->ahead_req;
-        if (to_worker) {                                       // the handle's worker thread starts on the table NOW, beside the launch call
-          for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) { h->fwd.coef[t] = cf.c[t]; h->fwd.dcoef[t] = cf.dc[t]; }
-          h->fwd.tab = tab; h->fwd.slot = slot; h->fwd.seq = seq;
-          handle_post_forward(h);
-        }
-        hipLaunchKernelGGL(kern, dim3(2 + ff.split + ff.n_helpers), dim3(BM_THREADS), lb, st, ki, S, cf, w.Kuu, w.dK, A, b, (int)M, w.bcrP, w.SP, w.alpha, w.logdets, info, s,
-                           tab_k, n_rec, h->node_rec_dev, w.bcrK, w.SK, w.dSK, h->done_dev + slot, seq,
-                           gpu_fwd ? dd_ready : (plan_first ? (const unsigned long long*)nullptr : h->ready_dev + slot), spin_limit, ff, box_k);
-        if (h->ahead_req) {
-          h->ahead = Handle::PendingAhead{true, slot, seq, tab, kind, ff.th.N, ff.th.Nw, ff.th.cw};
-          return check_launch("elbo chains (matrix cores, launched ahead of theta)");
-        }
-        if (gpu_fwd) return check_launch("elbo chains (matrix cores, forward pass on the GPU)");
-        if (to_worker) return check_launch("elbo chains (matrix cores, forward pass on the worker thread)");
-        const double t1 = host_times ? now_us() : 0.0;
-        if (!plan_first && h->defer_forward) {                  // the caller runs the forward pass later (asvgp_prior_publish): e.g. after
-          h->fwd.valid = true;                                   // enqueueing other work that should not wait 19 us behind it
-          for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) { h->fwd.coef[t] = cf.c[t]; h->fwd.dcoef[t] = cf.dc[t]; }
-          h->fwd.tab = tab; h->fwd.slot = slot; h->fwd.seq = seq;
-          return check_launch("elbo chains (matrix cores, forward pass deferred)");
-        }
-        if (!plan_first) (void)prior_plan_eval(h->plan, cf.c, cf.dc, tab);   // a non-positive pivot is reported through `info` by the kernel
-        if (host_times) {
-          static double acc_launch = 0.0, acc_plan = 0.0, acc_pre = 0.0, acc_acq = 0.0, acc_a = 0.0;
-          acc_acq += t_acq1 - t_acq0; acc_a += t_acq0 - t_enter;
-          static long calls = 0;
-          const double t2 = now_us();
-          acc_pre += t0 - t_enter; acc_launch += t1 - t0; acc_plan += t2 - t1;
-          if (++calls % 200 == 0) {
-            fprintf(stderr, "[entry -> acquire %.1f us, table acquire %.1f us] ", acc_a / 200, acc_acq / 200);
-            acc_a = acc_acq = 0.0;
-            fprintf(stderr, "[asvgp host times, mean of 200 calls] entry -> launch call %.1f us | launch call (%s) %.1f us | %s %.1f us\n", acc_pre / 200,
-                    plan_first ? "forward pass + hipLaunchKernel" : "hipLaunchKernel", acc_launch / 200, plan_first ? "-" : "forward pass", acc_plan / 200);
-            acc_launch = acc_plan = acc_pre = 0.0;
-          }
-        }
-        __atomic_store_n(h->ready_host + slot, seq, __ATOMIC_RELEASE);
-      }
-    }
-    if (!use_mfma) {
-    if (!gpu_fwd) {
-      (void)prior_plan_eval(h->plan, cf.c, cf.dc, tab);   // a non-positive pivot is reported through `info` by the kernel
-      __atomic_store_n(h->ready_host + slot, seq, __ATOMIC_RELEASE);
-    }
-    auto kern = big ? elbo_chains_kernel<K, HAS_BIG> : elbo_chains_kernel<K, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-    hipLaunchKernelGGL(kern, dim3(2 + ff.n_helpers), dim3(BCR_THREADS), lds_bytes, st, S, cf, w.Kuu, TANGENT ? w.dK : (double*)nullptr, A, b,
-                       (int)M, w.bcrP, w.SP, w.alpha, w.logdets, info, s,
-                       tab_k, n_rec, h->node_rec_dev, w.bcrK, w.SK, w.dSK,
-                       h->done_dev + slot, seq, (int)D, (int)(lds_bytes / sizeof(double)), ff);
-    }
-    if (scale_alpha) {
-      long n = M * D;
-      hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.alpha, 1.0 / s, n);
-    }
-    return check_launch("elbo chains (planned prior)");
-  }
-  // Kuu/dKuu (theta only) are written by the prior part, P = A/s + Kuu by the data part (which re-forms Kuu in registers)
-  const bool pfly = (part == 2) && use_bcr;   // data chain of the split call: P formed inside the BCR gathers
-  if (!pfly)
-    hipLaunchKernelGGL(elbo_prepare_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, S, cf, E, A, s,
-                       part == 2 ? w.LK : w.Kuu, part == 2 ? (double*)nullptr : w.dK, part == 1 ? (double*)nullptr : w.P);
-  if (h->sync_on && part == 1) (void)hipEventRecord(h->evK, st);
-  if (h->sync_on && part == 2) (void)hipStreamWaitEvent(st, h->evK, 0);
-  if (use_bcr) {
-    if (!fits) { set_error("BCR forced but needs %zu B of LDS", lds_bytes); return ASVGP_ERR_LDS_CAPACITY; }
-    hipError_t e = hipFuncSetAttribute(big ? reinterpret_cast<const void*>(elbo_bcr_kernel<K, TANGENT, HAS_BIG>) : reinterpret_cast<const void*>(elbo_bcr_kernel<K, TANGENT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-    if (part == 1 && TANGENT) {
-      if constexpr (TANGENT) {
-        auto kern = big ? elbo_bcr_prior_kernel<K, HAS_BIG> : elbo_bcr_prior_kernel<K, false>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-        hipLaunchKernelGGL(kern, dim3(1), dim3(BCR_THREADS), lds_bytes, st, w.Kuu, w.dK, (int)M, w.bcrK, w.SK, w.dSK, w.logdets, info,
-                           debug_env().bcr_stamps);
-      }
-    } else if (pfly) {
-      auto kern = big ? elbo_bcr_data_kernel<K, HAS_BIG> : elbo_bcr_data_kernel<K, false>;
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-      hipLaunchKernelGGL(kern, dim3(1), dim3(BCR_THREADS), lds_bytes, st, w.Kuu, A, b, (int)M, w.bcrP, w.SP, w.alpha, w.logdets, info,
-                         debug_env().bcr_stamps, s, (int)D, (int)(lds_bytes / sizeof(double)));
-    } else {
-      auto kern = big ? elbo_bcr_kernel<K, TANGENT, HAS_BIG> : elbo_bcr_kernel<K, TANGENT, false>;
-      hipLaunchKernelGGL(kern, dim3(part == 0 ? 2 : 1), dim3(BCR_THREADS), lds_bytes, st, w.Kuu, w.dK,
-                         w.P, b, (int)M, w.bcrK, w.bcrP, w.SK, w.dSK, w.SP, w.alpha, w.logdets, info,
-                         debug_env().bcr_stamps, part == 2 ? 1 : 0, (int)D, (int)(lds_bytes / sizeof(double)));
-    }
-    if (part == 1) {
-      if (h->sync_on) (void)hipEventRecord(h->evP, st);
-      return check_launch("elbo prior chain");
-    }
-  } else if (D == 1) {
-    hipLaunchKernelGGL((elbo_factor_kernel<K, TANGENT, true>), dim3(2), dim3(64), 0, st, w.Kuu, w.dK, w.P, w.LK, w.dLK,
-                       w.LP, b, w.c, (int)M, info);
-    hipLaunchKernelGGL((elbo_inverse_kernel<K, TANGENT, true>), dim3(2), dim3(64), 0, st, w.LK, w.dLK, w.LP, w.SK,
-                       w.dSK, w.SP, w.c, w.alpha, (int)M);
-  } else {
-    hipLaunchKernelGGL((elbo_factor_kernel<K, TANGENT, false>), dim3(2), dim3(64), 0, st, w.Kuu, w.dK, w.P, w.LK,
-                       w.dLK, w.LP, b, w.c, (int)M, info);
-    hipLaunchKernelGGL(elbo_trsv_kernel<K>, dim3((unsigned)D), dim3(64), 0, st, w.LP, (int)M, b, w.c, D, 0, 1.0);
-    hipLaunchKernelGGL((elbo_inverse_kernel<K, TANGENT, false>), dim3(2), dim3(64), 0, st, w.LK, w.dLK, w.LP, w.SK,
-                       w.dSK, w.SP, w.c, w.alpha, (int)M);
-    hipLaunchKernelGGL(elbo_trsv_kernel<K>, dim3((unsigned)D), dim3(64), 0, st, w.LP, (int)M, w.c, w.alpha, D, 1, 1.0);
-  }
-  // c = L_P^-1 b / s (gpr.py:75), alpha = P^-1 b / s
-  long n = M * D;
-  if (!use_bcr) hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.c, 1.0 / s, n);
-  if (!use_bcr || scale_alpha)   // (the BCR + ELBO path leaves alpha unscaled and lets the finalize apply 1/s)
-    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.alpha, 1.0 / s, n);
-  return check_launch("elbo chains");
+  set_error("elbo chains: no launcher for this plan in this unit");
+  return ASVGP_ERR_UNSUPPORTED;
 }
 
 template <int K>
@@ -1073,18 +1205,19 @@ int ElboLauncher<K>::run(Handle* h, const double* stats, const double* S, int ki
                          double* out, int* info, void* ws, hipStream_t st, int part) {
   {
     Ws w = carve(ws, M, K, D);
-    bool bcr = false;
+    ChainPlan p;
     h->mirror_pending = 0;                                    // (set again by the one launch that writes the mirror)
     // weighted statistics (asvgp_set_weight_sums): the row count is N+, the trace term takes sum w, the bound gains 1/2 D sum log w
     ElboScalars th{v, l, s, (double)N, (double)N, 0.0};
     if (h->w_set) { th.N = h->w_npos; th.Nw = h->w_sum; th.cw = 0.5 * (double)D * h->w_sumlog; }
     const int fin_blocks = (int)((M + 255) / 256 < 64 ? (M + 255) / 256 : 64);
     static_assert(BCR_THREADS == 256, "the fused finalize shares the chain kernel's workgroup size");
-    FusedFin ff{stats, th, 1.0 / s, w.fin, reinterpret_cast<unsigned*>(w.fin + 16), reinterpret_cast<unsigned*>(w.fin + 18), nullptr, out, D, 0, 0};
-    int rc = run_chains<K, true>(h, stats, S, kind, v, l, s, M, D, w, info, st, bcr, part, false, part == 1 ? nullptr : &ff);
+    const FusedFin ff{stats, th, 1.0 / s, w.fin, reinterpret_cast<unsigned*>(w.fin + 16), reinterpret_cast<unsigned*>(w.fin + 18), nullptr, out, D, 0, 0};
+    int rc = run_chains<K, true>(h, stats, S, kind, v, l, s, M, D, w, info, st, p, part, part == 1 ? nullptr : &ff);
     if (rc || (part == 1)) return rc;
-    if (ff.finalize < 0) return check_launch("elbo_grad_1d (fused)");
-    if (h->sync_on && part == 2 && bcr && h->evP) (void)hipStreamWaitEvent(st, h->evP, 0);
+    if (p.path == PATH_PLANNED_BCR || p.path == PATH_PLANNED_MFMA) return check_launch("elbo_grad_1d (fused)");   // (the finalize rode along)
+    const bool bcr = p.path != PATH_SWEEPS;
+    if (h->sync_on && p.path == PATH_BCR_DATA && h->evP) (void)hipStreamWaitEvent(st, h->evP, 0);
     hipLaunchKernelGGL(elbo_finalize_kernel<K>, dim3(fin_blocks), dim3(256), 0, st, stats, w.Kuu, w.dK, w.LK, w.LP, w.SK,
                        w.dSK, w.SP, w.c, w.alpha, bcr ? w.logdets : (const double*)nullptr, M, K, D, th,
                        bcr ? 1.0 / s : 1.0, w.fin, reinterpret_cast<unsigned*>(w.fin + 16), out);
@@ -1096,8 +1229,8 @@ int PostLauncher<K>::run(Handle* h, const double* stats, const double* S, int ki
                          double* alpha, double* W, int* info, void* ws, hipStream_t st, double* Pinv) {
   {
     Ws w = carve(ws, M, K, D);
-    bool bcr = false;
-    int rc = run_chains<K, false>(h, stats, S, kind, v, l, s, M, D, w, info, st, bcr);
+    ChainPlan p;
+    int rc = run_chains<K, false>(h, stats, S, kind, v, l, s, M, D, w, info, st, p);
     if (rc) return rc;
     long E = (long)(K + 1) * M;
     hipLaunchKernelGGL(scale_sub_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, w.SP, w.SK, W, E);
@@ -1270,31 +1403,29 @@ int KuuInvLauncher<K>::run(Handle* h, const double* S, int kind, double v, doubl
                      (double*)nullptr);
   const bool have_plan = h->plan && prior_plan_M(h->plan) == M && prior_plan_k(h->plan) == K && prior_plan_terms(h->plan) == cf.n;
   if (have_plan && h->band_algo != 1 && h->band_algo != 2) {
-    unsigned long long seq = 0;
-    int slot = 0;
-    double* tab = handle_table_acquire(h, &seq, &slot);
-    const double* tab_k = h->tab_dev + (size_t)slot * h->slot_doubles;
+    TableSlot slot(h);
+    const double* tab_k = h->tab_dev + (size_t)slot.slot * h->slot_doubles;
     if (h->prior_forward_gpu) {
       double* t = nullptr;
-      rc = handle_prior_dd_forward(h, cf.c, cf.dc, slot, st, &t);
+      rc = handle_prior_dd_forward(h, cf.c, cf.dc, slot.slot, st, &t);
       if (rc) return rc;
       tab_k = t;
     } else {
-      (void)prior_plan_eval(h->plan, cf.c, cf.dc, tab);
+      (void)prior_plan_eval(h->plan, cf.c, cf.dc, slot.tab);
     }
     const int n_rec = prior_plan_nrec(h->plan);
     const size_t lds_bytes = sizeof(double) * bcr_pre_lds_doubles(K, n_rec);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kuu_inverse_pre_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
+    rc = grant_lds(reinterpret_cast<const void*>(kuu_inverse_pre_kernel<K>), lds_bytes);
+    if (rc) return rc;
     hipLaunchKernelGGL(kuu_inverse_pre_kernel<K>, dim3(1), dim3(BCR_THREADS), lds_bytes, st, tab_k, n_rec,
-                       h->node_rec_dev, (int)M, w.bcrK, SK, dSK, logdet2, info, h->done_dev + slot, seq);
-    return check_launch("kuu_inverse_band_1d (planned)");
+                       h->node_rec_dev, (int)M, w.bcrK, SK, dSK, logdet2, info, h->done_dev + slot.slot, slot.seq);
+    return slot.launched(check_launch("kuu_inverse_band_1d (planned)"));
   }
   const size_t ldsK = sizeof(double) * bcr_lds_doubles<Dual, K, 0>(nb);
-  if (ldsK <= 160 * 1024 - 256 && h->band_algo != 1) {
+  if (ldsK <= LDS_BYTES - 256 && h->band_algo != 1) {
     auto kern = elbo_bcr_prior_kernel<K, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsK);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
+    rc = grant_lds(reinterpret_cast<const void*>(kern), ldsK);
+    if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(1), dim3(BCR_THREADS), ldsK, st, Kuu, dK, (int)M, w.bcrK, SK, dSK, logdet2, info, 0);
     return check_launch("kuu_inverse_band_1d (BCR)");
   }
@@ -1321,16 +1452,10 @@ int elbo_publish_theta(Handle* h, double v, double l, double s, bool withdraw) {
   for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) cf.c[t] = cf.dc[t] = 0.0;
   const int rc = asvgp_matern_coeffs(a.kind, v, l, cf.c, cf.dc, &cf.n);
   if (rc) { __atomic_store_n(&bh->seq, ~0ull, __ATOMIC_RELEASE); return rc; }
-  constexpr int K = 4;
-  long lo = 0, hi = 0, lo2 = 0, hi2 = 0;
-  double bnd2[2 * PRIOR_BND_DIAGS * PRIOR_BND];
+  long lo = 0, hi = 0;
   for (int i = 0; i < 8; ++i) { bh->k[i] = 0.0; bh->dk[i] = 0.0; }
   prior_plan_interior_kuu(h->plan, cf.c, bh->k, &lo, &hi, bh->bnd);
-  prior_plan_interior_kuu(h->plan, cf.dc, bh->dk, &lo2, &hi2, bnd2);
-  for (int sd = 0; sd < 2; ++sd)
-    for (int d = 0; d <= K; ++d)
-      for (int cI = 0; cI < KI_DKB; ++cI)
-        bh->dkb[(sd * 5 + d) * KI_DKB + cI] = bnd2[(size_t)(sd * PRIOR_BND_DIAGS + d) * PRIOR_BND + cI];
+  interior_dkuu(h->plan, cf.dc, bh->dk, bh->dkb);
   for (int t = 0; t < ASVGP_MAX_KUU_TERMS; ++t) bh->dc[t] = cf.dc[t];
   bh->s = s; bh->alpha_scale = 1.0 / s; bh->v = v; bh->l = l; bh->N = a.N; bh->Nw = a.Nw; bh->cw = a.cw;
   __atomic_store_n(&bh->seq, a.seq, __ATOMIC_RELEASE);          // the kernel proceeds: P chain at once, the Kuu workgroup waits for the table
@@ -1379,11 +1504,23 @@ static int elbo_args_ok(const void* stats, const void* S, const void* out, int64
   return ASVGP_OK;
 }
 
-// asvgp_elbo_grad_1d + the host's read of its result in ONE call (an optimiser's evaluation, example.py:31-32): launch with the result
-// mirror armed, then poll the mirror from C.  result[0..9] = [out[0..7], info[0], info[1]].
 extern "C" int asvgp_elbo_grad_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
                                   double lengthscale, double noise_variance, int64_t N, int64_t M, int k, int64_t D,
-                                  double* out, int* info, void* workspace, size_t workspace_bytes, asvgp_stream_t stream);
+                                  double* out, int* info, void* workspace, size_t workspace_bytes,
+                                  asvgp_stream_t stream) {
+  int rc = elbo_args_ok(stats, static_bands, out, M, k, D, variance, lengthscale, noise_variance, workspace,
+                        workspace_bytes, info, "elbo_grad_1d");
+  if (rc) return rc;
+  Handle* h = as_handle(handle);
+  { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }   // (a deferred Phi reduce into THIS buffer goes first)
+  hipStream_t st = as_stream(stream);
+  return for_bandwidth(k, [&](auto kk) {
+    return ElboLauncher<decltype(kk)::value>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)N, (long)M, (long)D, out, info, workspace, st, 0);
+  });
+}
+
+// asvgp_elbo_grad_1d + the host's read of its result in ONE call (an optimiser's evaluation, example.py:31-32): launch with the result
+// mirror armed, then poll the mirror from C.  result[0..9] = [out[0..7], info[0], info[1]].
 extern "C" int asvgp_result_mirror_read(asvgp_handle_t handle, uint64_t token, double* result10, double timeout_seconds) {
   Handle* h = as_handle(handle);
   if (!result10) { set_error("result_mirror_read: bad argument"); return ASVGP_ERR_BAD_ARG; }
@@ -1438,22 +1575,6 @@ extern "C" int asvgp_elbo_grad_host_1d(asvgp_handle_t handle, const double* stat
   return asvgp_result_mirror_read(handle, h->mirror_pending, result10, timeout_seconds);
 }
 
-extern "C" int asvgp_elbo_grad_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
-                                  double lengthscale, double noise_variance, int64_t N, int64_t M, int k, int64_t D,
-                                  double* out, int* info, void* workspace, size_t workspace_bytes,
-                                  asvgp_stream_t stream) {
-  int rc = elbo_args_ok(stats, static_bands, out, M, k, D, variance, lengthscale, noise_variance, workspace,
-                        workspace_bytes, info, "elbo_grad_1d");
-  if (rc) return rc;
-  Handle* h = as_handle(handle);
-  { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }   // (a deferred Phi reduce into THIS buffer goes first)
-  hipStream_t st = as_stream(stream);
-#define ELBO_CASE(KK) case KK: return ElboLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)N, (long)M, (long)D, out, info, workspace, st, 0);
-  switch (k) { ELBO_CASE(1) ELBO_CASE(2) ELBO_CASE(3) ELBO_CASE(4) ELBO_CASE(5) ELBO_CASE(6) }
-#undef ELBO_CASE
-  return ASVGP_ERR_UNSUPPORTED;
-}
-
 extern "C" int asvgp_elbo_prior_chain_1d(asvgp_handle_t handle, const double* static_bands, int kind, double variance, double lengthscale,
                                          double noise_variance, int64_t M, int k, int64_t D, int* info, void* workspace,
                                          size_t workspace_bytes, asvgp_stream_t stream) {
@@ -1462,10 +1583,9 @@ extern "C" int asvgp_elbo_prior_chain_1d(asvgp_handle_t handle, const double* st
   if (rc) return rc;
   Handle* h = as_handle(handle);
   hipStream_t st = as_stream(stream);
-#define ELBO_CASE(KK) case KK: return ElboLauncher<KK>::run(h, nullptr, static_bands, kind, variance, lengthscale, noise_variance, 0, (long)M, (long)D, nullptr, info, workspace, st, 1);
-  switch (k) { ELBO_CASE(1) ELBO_CASE(2) ELBO_CASE(3) ELBO_CASE(4) ELBO_CASE(5) ELBO_CASE(6) }
-#undef ELBO_CASE
-  return ASVGP_ERR_UNSUPPORTED;
+  return for_bandwidth(k, [&](auto kk) {
+    return ElboLauncher<decltype(kk)::value>::run(h, nullptr, static_bands, kind, variance, lengthscale, noise_variance, 0, (long)M, (long)D, nullptr, info, workspace, st, 1);
+  });
 }
 
 extern "C" int asvgp_elbo_data_chain_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
@@ -1478,10 +1598,9 @@ extern "C" int asvgp_elbo_data_chain_1d(asvgp_handle_t handle, const double* sta
   Handle* h = as_handle(handle);
   { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }   // (a deferred Phi reduce into THIS buffer goes first)
   hipStream_t st = as_stream(stream);
-#define ELBO_CASE(KK) case KK: return ElboLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)N, (long)M, (long)D, out, info, workspace, st, 2);
-  switch (k) { ELBO_CASE(1) ELBO_CASE(2) ELBO_CASE(3) ELBO_CASE(4) ELBO_CASE(5) ELBO_CASE(6) }
-#undef ELBO_CASE
-  return ASVGP_ERR_UNSUPPORTED;
+  return for_bandwidth(k, [&](auto kk) {
+    return ElboLauncher<decltype(kk)::value>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)N, (long)M, (long)D, out, info, workspace, st, 2);
+  });
 }
 
 extern "C" int asvgp_kuu_inverse_band_1d(asvgp_handle_t handle, const double* static_bands, int kind, double variance, double lengthscale,
@@ -1495,10 +1614,9 @@ extern "C" int asvgp_kuu_inverse_band_1d(asvgp_handle_t handle, const double* st
   if (!workspace || workspace_bytes < asvgp_elbo_workspace_bytes(M, k, 1)) { set_error("kuu_inverse_band_1d: workspace too small"); return ASVGP_ERR_WORKSPACE; }
   Handle* h = as_handle(handle);
   hipStream_t st = as_stream(stream);
-#define KINV_CASE(KK) case KK: return KuuInvLauncher<KK>::run(h, static_bands, kind, variance, lengthscale, (long)M, Kuu, dKuu_dl, S, dS_dl, logdet2, info, workspace, st);
-  switch (k) { KINV_CASE(1) KINV_CASE(2) KINV_CASE(3) KINV_CASE(4) KINV_CASE(5) KINV_CASE(6) }
-#undef KINV_CASE
-  return ASVGP_ERR_UNSUPPORTED;
+  return for_bandwidth(k, [&](auto kk) {
+    return KuuInvLauncher<decltype(kk)::value>::run(h, static_bands, kind, variance, lengthscale, (long)M, Kuu, dKuu_dl, S, dS_dl, logdet2, info, workspace, st);
+  });
 }
 
 extern "C" int asvgp_posterior_prepare_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,
@@ -1512,10 +1630,9 @@ extern "C" int asvgp_posterior_prepare_1d(asvgp_handle_t handle, const double* s
   Handle* h = as_handle(handle);
   { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }   // (a deferred Phi reduce into THIS buffer goes first)
   hipStream_t st = as_stream(stream);
-#define POST_CASE(KK) case KK: return PostLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st);
-  switch (k) { POST_CASE(1) POST_CASE(2) POST_CASE(3) POST_CASE(4) POST_CASE(5) POST_CASE(6) }
-#undef POST_CASE
-  return ASVGP_ERR_UNSUPPORTED;
+  return for_bandwidth(k, [&](auto kk) {
+    return PostLauncher<decltype(kk)::value>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st);
+  });
 }
 
 // asvgp_posterior_prepare_1d with band(P^-1) as a third output (the leave-one-out leverages of asvgp_loo_1d need P^-1 itself)
@@ -1530,10 +1647,9 @@ extern "C" int asvgp_posterior_prepare_loo_1d(asvgp_handle_t handle, const doubl
   Handle* h = as_handle(handle);
   { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }
   hipStream_t st = as_stream(stream);
-#define POST_CASE(KK) case KK: return PostLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st, Pinv_band);
-  switch (k) { POST_CASE(1) POST_CASE(2) POST_CASE(3) POST_CASE(4) POST_CASE(5) POST_CASE(6) }
-#undef POST_CASE
-  return ASVGP_ERR_UNSUPPORTED;
+  return for_bandwidth(k, [&](auto kk) {
+    return PostLauncher<decltype(kk)::value>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, info, workspace, st, Pinv_band);
+  });
 }
 
 extern "C" size_t asvgp_posterior_cov_workspace_bytes(int64_t M, int k, int64_t D) {
@@ -1556,10 +1672,32 @@ extern "C" int asvgp_posterior_cov_prepare_1d(asvgp_handle_t handle, const doubl
   Handle* h = as_handle(handle);
   { const int rcf = handle_flush_phi_reduce(h, stats, as_stream(stream)); if (rcf) return rcf; }
   hipStream_t st = as_stream(stream);
-#define COV_CASE(KK) case KK: return PostCovLauncher<KK>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, W_dense, info, workspace, st);
-  switch (k) { COV_CASE(1) COV_CASE(2) COV_CASE(3) COV_CASE(4) COV_CASE(5) COV_CASE(6) }
-#undef COV_CASE
-  return ASVGP_ERR_UNSUPPORTED;
+  return for_bandwidth(k, [&](auto kk) {
+    return PostCovLauncher<decltype(kk)::value>::run(h, stats, static_bands, kind, variance, lengthscale, noise_variance, (long)M, (long)D, alpha, W, W_dense, info, workspace, st);
+  });
+}
+
+// Host-only: the plan run_chains would make for these inputs - the same plan_chains, no handle, no device
+extern "C" int asvgp_elbo_launch_plan_host(int band_algorithm, int have_plan, int n_rec, int interior, int64_t M, int k, int64_t D, int part, int tangent,
+                                           int fused_finalize, int ahead, int prior_forward_gpu, int forward_worker, int defer_forward, int no_split,
+                                           int plan_first, int64_t* plan12_host) {
+  if (!plan12_host || M < 1 || D < 1 || part < 0 || part > 2 || band_algorithm < 0 || band_algorithm > 4) {
+    set_error("elbo_launch_plan_host: bad argument");
+    return ASVGP_ERR_BAD_ARG;
+  }
+  const ChainPlanIn in{band_algorithm, have_plan != 0, n_rec, interior != 0, (long)M, (long)D, part, fused_finalize != 0, ahead != 0,
+                       prior_forward_gpu != 0, forward_worker != 0, defer_forward != 0, no_split != 0, plan_first != 0};
+  ChainPlan p{};
+  p.status = ASVGP_ERR_UNSUPPORTED;
+  snprintf(p.msg, sizeof(p.msg), "elbo_launch_plan_host: bandwidth %d outside 1..%d", k, (int)ASVGP_MAX_ORDER);
+  (void)for_bandwidth(k, [&](auto kk) {
+    p = tangent ? plan_chains<decltype(kk)::value, true>(in) : plan_chains<decltype(kk)::value, false>(in);
+    return 0;
+  });
+  const int64_t f[12] = {p.status, p.path, p.part, p.nothing, p.big, (int64_t)p.lds_bytes, p.grid, p.n_helpers, p.split, p.fwd, p.scale_alpha, p.scale_c};
+  for (int i = 0; i < 12; ++i) plan12_host[i] = f[i];
+  if (p.status) set_error("%s", p.msg);
+  return p.status;
 }
 
 #endif  // !ASVGP_ELBO_ONLY_K

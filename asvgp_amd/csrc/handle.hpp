@@ -125,5 +125,21 @@ int elbo_publish_theta(Handle* h, double v, double l, double s, bool withdraw);
 
 // next table slot for writing: waits (bounded) until the GPU has consumed the slot's previous table
 double* handle_table_acquire(Handle* h, unsigned long long* seq_out, int* slot_out);
+// A slot of the ring from its acquisition to its hand-over.  A slot whose kernel never reports leaves handle_quiesce and the 16th-next
+// acquire spinning for 2 s, so unless the slot is handed over - a kernel was launched that will store done[slot] (launched(ASVGP_OK)),
+// among them the launch a pending launch-ahead record waits for - leaving scope marks it consumed and ready: every error return between
+// the acquire and the launch is safe.  Acquire only once the call can no longer be refused.
+struct TableSlot {
+  Handle* h; unsigned long long seq = 0; int slot = 0; double* tab; bool owned = true;
+  explicit TableSlot(Handle* hh) : h(hh) { tab = handle_table_acquire(h, &seq, &slot); }
+  TableSlot(const TableSlot&) = delete;
+  TableSlot& operator=(const TableSlot&) = delete;
+  int launched(int rc) { if (rc == ASVGP_OK) owned = false; return rc; }   // rc: the launch's status, passed through
+  ~TableSlot() {
+    if (!owned) return;                    // (no kernel consumes this slot)
+    __atomic_store_n(h->ready_host + slot, seq, __ATOMIC_RELEASE);
+    __atomic_store_n(h->done_host + slot, seq, __ATOMIC_RELEASE);
+  }
+};
 
 }  // namespace asvgp

@@ -129,17 +129,14 @@ extern "C" int asvgp_prior_forward_device(asvgp_handle_t handle, const double* c
   const size_t n = prior_plan_table_doubles(h->plan);
   if (table_doubles < n) { set_error("prior_forward_device: table too small"); return ASVGP_ERR_WORKSPACE; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  unsigned long long seq = 0;
-  int slot = 0;
-  (void)handle_table_acquire(h, &seq, &slot);
+  TableSlot slot(h);                         // (no kernel consumes this slot: released on every return)
   double* tab = nullptr;
-  int rc = handle_prior_dd_forward(h, coef_host, dcoef_dl_host, slot, st, &tab);
+  int rc = handle_prior_dd_forward(h, coef_host, dcoef_dl_host, slot.slot, st, &tab);
   if (rc) return rc;
   if (hipMemcpyAsync(table_host, tab, sizeof(double) * n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     set_error("prior_forward_device: copy failed: %s", hipGetErrorString(hipGetLastError()));
     return ASVGP_ERR_HIP;
   }
-  __atomic_store_n(h->done_host + slot, seq, __ATOMIC_RELEASE);   // (no kernel consumes this slot)
   return ASVGP_OK;
 }
 
@@ -152,16 +149,13 @@ extern "C" int asvgp_prior_forward_stamps(asvgp_handle_t handle, const double* c
   unsigned long long* dev = nullptr;
   if (hipMalloc(reinterpret_cast<void**>(&dev), sizeof(unsigned long long) * 64) != hipSuccess) { set_error("prior_forward_stamps: hipMalloc failed"); return ASVGP_ERR_HIP; }
   (void)hipMemsetAsync(dev, 0, sizeof(unsigned long long) * 64, st);
-  unsigned long long seq = 0;
-  int slot = 0;
-  (void)handle_table_acquire(h, &seq, &slot);
+  TableSlot slot(h);                         // (no kernel consumes this slot)
   double* tab = nullptr;
-  int rc = handle_prior_dd_forward(h, coef_host, dcoef_dl_host, slot, st, &tab, dev);
+  int rc = handle_prior_dd_forward(h, coef_host, dcoef_dl_host, slot.slot, st, &tab, dev);
   if (rc == ASVGP_OK && (hipMemcpyAsync(out64, dev, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
     set_error("prior_forward_stamps: copy failed");
     rc = ASVGP_ERR_HIP;
   }
   (void)hipFree(dev);
-  __atomic_store_n(h->done_host + slot, seq, __ATOMIC_RELEASE);
   return rc;
 }

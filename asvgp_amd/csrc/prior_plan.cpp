@@ -178,11 +178,14 @@ int prior_plan_mantissa_bits() { return LDBL_MANT_DIG; }
 // (col - hi)] (col >= hi; entries below the matrix are 0).  All formed with the rounding sequence of inducing_features.py:12-44 (this
 // file is compiled with -ffp-contract=off): bit for bit what the device assembly writes.  *hi <= *lo: no usable interior (a boundary
 // wider than PRIOR_BND columns, or no Toeplitz structure) - the caller keeps the assembled band.
+bool prior_plan_interior(const PriorPlan* p) {
+  return p->int_hi > p->int_lo && p->int_lo <= PRIOR_BND && p->M - p->int_hi <= PRIOR_BND && p->B + 1 <= PRIOR_BND_DIAGS;
+}
 void prior_plan_interior_kuu(const PriorPlan* p, const double* coef, double* kuu_diag, long* lo, long* hi, double* bnd) {
   const int B = p->B;
   const long M = p->M;
   *lo = 0; *hi = 0;
-  if (p->int_hi <= p->int_lo || p->int_lo > PRIOR_BND || M - p->int_hi > PRIOR_BND || B + 1 > PRIOR_BND_DIAGS) return;
+  if (!prior_plan_interior(p)) return;
   auto entry = [&](int d, long col) -> double {
     if (col + d >= M) return 0.0;
     const double* S = p->S.data();

@@ -9,7 +9,7 @@
 
 #include "../../include/asvgp_hip.h"
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 #define ASVGP_HD __host__ __device__
 #else
 #define ASVGP_HD
@@ -35,6 +35,7 @@ void prior_plan_destroy(PriorPlan* p);
 // (bnd: 2 * PRIOR_BND_DIAGS * PRIOR_BND doubles; layout in prior_plan.cpp); *hi <= *lo: not available
 constexpr int PRIOR_BND = 16, PRIOR_BND_DIAGS = 8;
 void prior_plan_interior_kuu(const PriorPlan* p, const double* coef, double* kuu_diag, long* lo, long* hi, double* bnd);
+bool prior_plan_interior(const PriorPlan* p);                 // is it available (theta plays no part: decided when the plan was made)
 int prior_plan_nrec(const PriorPlan* p);
 int prior_plan_nb(const PriorPlan* p);
 long prior_plan_M(const PriorPlan* p);

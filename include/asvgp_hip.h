@@ -277,8 +277,8 @@ size_t asvgp_elbo_workspace_bytes(int64_t M, int k, int64_t D);   /* the workspa
  * prior chain (asvgp_prior_plan_1d): forward pass of the Kuu chain on the host in long double over the O(log M) distinct
  * nodes, backward (selected inverse) pass on the GPU, 4 = the planned chains with every 4 x 4 block product on the matrix cores
  * (v_mfma_f64_4x4x4f64; k = 4, D = 1, M <= 2048, asvgp_elbo_grad_1d).  Auto = 4 where it applies, else 3 when the handle holds a
- * matching plan, else 2 when both chains fit the 160 KiB LDS and D == 1, else 1.  2 / 3 return ASVGP_ERR_LDS_CAPACITY when the chains
- * do not fit.  info[1] < 0 after a fused launch: the launch gave up waiting for its helper workgroups (they never became resident);
+ * matching plan and the P chain fits the 160 KiB LDS, else 2 when both chains fit it, else 1 (asvgp_elbo_launch_plan_host shows the
+ * choice).  2 / 3 return ASVGP_ERR_LDS_CAPACITY when the chains do not fit.  info[1] < 0 after a fused launch: the launch gave up waiting for its helper workgroups (they never became resident);
  * its results are to be discarded, the workspace zero-filled again and the step re-issued (asvgp_amd.GPR_1d does that through
  * algorithm 1). */
 int asvgp_set_band_algorithm(asvgp_handle_t handle, int algo);
@@ -312,6 +312,22 @@ int asvgp_prior_forward_device(asvgp_handle_t handle, const double* coef_host, c
  * forward pass walks.  ints / doubles NULL: sizes only.  For the CPU tests. */
 int asvgp_prior_plan_image_host(const double* static_bands_host, int n_terms, int64_t M, int k, int* ints, size_t* n_ints,
                                 double* doubles, size_t* n_doubles);
+/* Host-only: the launch plan of the fused drivers below (asvgp_elbo_grad_1d, the split entry points, asvgp_posterior_prepare_1d) for
+ * these inputs, as the launchers themselves compute it before they take a table slot or launch anything - no handle, no device.
+ * Inputs: the handle's band algorithm; whether it holds a plan for this (M, k, kernel), the plan's record count and whether its static
+ * bands have a Toeplitz interior; M, k, D; part (0 whole, 1 prior half, 2 data half); tangent = 1 for the ELBO + gradient launchers, 0 for
+ * the posterior ones; whether the caller offers the fused finalize (asvgp_elbo_grad_1d and the data half do); a launch-ahead request;
+ * asvgp_set_prior_forward(h, 1); asvgp_set_deferred_forward_pass 2 / 1; the ASVGP_NO_SPLIT and ASVGP_PLAN_FIRST measurement aids.
+ * plan12_host: [0] status, [1] path (0 sequential sweeps, 1 block cyclic reduction, 2 its prior half, 3 its data half, 4 planned prior
+ * chain on the BCR kernel, 5 planned chains on the matrix cores), [2] the effective part, [3] 1 = nothing to do (part 1 of a path without
+ * split scheduling), [4] BIG layout, [5] dynamic LDS bytes, [6] workgroups of the chains' kernel, [7] helper workgroups among them,
+ * [8] P chain split over two workgroups, [9] who runs the forward pass of the planned Kuu chain (0 nobody, 1 the calling thread behind
+ * the launch, 2 the calling thread in front of it, 3 the caller through asvgp_prior_publish, 4 the worker thread, 5 the GPU,
+ * 6 asvgp_elbo_publish_theta), [10] / [11] alpha / c scaled by 1 / noise variance behind the chains.  Returns the status: ASVGP_OK, or
+ * what the launch would be refused with (asvgp_last_error_string says why).  For the CPU tests. */
+int asvgp_elbo_launch_plan_host(int band_algorithm, int have_plan, int n_rec, int interior, int64_t M, int k, int64_t D, int part, int tangent,
+                                int fused_finalize, int ahead, int prior_forward_gpu, int forward_worker, int defer_forward, int no_split,
+                                int plan_first, int64_t* plan12_host);
 /* Diagnostics: s_memtime stamps of thread 0 along one GPU forward pass (out64: 64 values, [63] = how many; tools/prior_dd_probe.py). */
 int asvgp_prior_forward_stamps(asvgp_handle_t handle, const double* coef_host, const double* dcoef_dl_host, uint64_t* out64, void* stream);
 int asvgp_elbo_grad_1d(asvgp_handle_t handle, const double* stats, const double* static_bands, int kind, double variance,

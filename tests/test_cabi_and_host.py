@@ -384,6 +384,128 @@ def test_prior_plan_device_image_is_consistent_with_the_host_plan(lib, order, M,
                 assert codes[r, cc] == 0 and acc == K[r - cc, cc], (r, cc)
 
 
+SWEEPS, BCR, BCR_PRIOR, BCR_DATA, PLANNED_BCR, MATRIX_CORE = range(6)          # plan12[1] of asvgp_elbo_launch_plan_host
+FWD_NOBODY, FWD_INLINE, FWD_BEFORE, FWD_CALLER, FWD_WORKER, FWD_GPU, FWD_PUBLISH_THETA = range(7)   # plan12[9]
+OK, BAD_ARG, UNSUPPORTED, LDS_CAPACITY = 0, -1, -2, -3
+_N_REC = {}
+
+
+def _launch_plan(lib, M, k, algo=0, plan=True, D=1, part=0, tangent=1, fin=None, **flags):
+    """(status, fields by name) of asvgp_elbo_launch_plan_host.  plan=True: the handle holds the plan of the uniform B-spline basis of this
+    (M, k) - its record count from the host planner, its static bands Toeplitz in the interior.  fin=None: offered as the entry points do
+    (the ELBO + gradient launcher, except in the prior half)."""
+    n_rec = 0
+    if plan:
+        if (M, k) not in _N_REC:
+            bs = O.Basis(k, 0, 1, M)
+            terms = O.kuu_terms(1, 0.9, 0.07)
+            S = np.ascontiguousarray(np.stack([getattr(bs, nm) for nm, _, _ in terms]))
+            ni, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            assert lib.asvgp_prior_plan_image_host(S.ctypes.data, len(terms), M, k, None, ctypes.byref(ni), None, ctypes.byref(nd)) == 0
+            ints = np.zeros(ni.value, dtype=np.int32)
+            dbl = np.zeros(max(nd.value, 1))
+            assert lib.asvgp_prior_plan_image_host(S.ctypes.data, len(terms), M, k, ints.ctypes.data, ctypes.byref(ni), dbl.ctypes.data, ctypes.byref(nd)) == 0
+            _N_REC[(M, k)] = int(ints[3])
+        n_rec = _N_REC[(M, k)]
+    if fin is None:
+        fin = 1 if tangent and part != 1 else 0
+    f = dict(ahead=0, gpu=0, worker=0, defer=0, no_split=0, plan_first=0)
+    f.update(flags)
+    out = np.full(12, -99, dtype=np.int64)
+    rc = lib.asvgp_elbo_launch_plan_host(algo, int(plan), n_rec, int(plan), M, k, D, part, tangent, fin, f["ahead"], f["gpu"], f["worker"], f["defer"],
+                                         f["no_split"], f["plan_first"], out.ctypes.data)
+    names = ("status", "path", "part", "nothing", "big", "lds", "grid", "helpers", "split", "fwd", "scale_alpha", "scale_c")
+    p = dict(zip(names, (int(v) for v in out)))
+    assert p["status"] == rc
+    return rc, p
+
+
+def test_fused_elbo_launch_plan_follows_the_documented_rules(lib):
+    """asvgp_elbo_launch_plan_host is the plan_chains the launchers of csrc/elbo.hip call before they take a table slot or launch anything.
+    Which path a given (algorithm, plan, M, k, D, entry point, flags) takes, written down from the rules (include/asvgp_hip.h:
+    asvgp_set_band_algorithm, asvgp_elbo_grad_ahead_1d) - the cases sit away from the LDS thresholds, so no expectation is a byte count."""
+    def plan(*a, **kw):
+        rc, p = _launch_plan(lib, *a, **kw)
+        assert rc == OK, lib.asvgp_last_error_string()
+        return p
+
+    def refused(*a, **kw):
+        return _launch_plan(lib, *a, **kw)[0]
+
+    # the headline shape: both chains on the matrix cores, the P chain on two workgroups, no helpers, forward pass behind the launch
+    p = plan(2048, 4)
+    assert (p["path"], p["split"], p["grid"], p["helpers"], p["fwd"], p["nothing"]) == (MATRIX_CORE, 1, 3, 0, FWD_INLINE, 0)
+    assert (p["scale_alpha"], p["scale_c"]) == (0, 0) and 0 < p["lds"] <= 160 * 1024
+    p = plan(2048, 4, no_split=1)
+    assert (p["path"], p["split"], p["grid"]) == (MATRIX_CORE, 0, 2)
+    p = plan(64, 4)
+    assert (p["path"], p["split"], p["grid"]) == (MATRIX_CORE, 0, 2)
+    assert plan(2048, 4, algo=4)["path"] == MATRIX_CORE
+    # where the matrix cores do not apply: the planned chain on the BCR kernel, forward pass in front of the launch, up to six helpers
+    p = plan(2052, 4)                                              # 513 block nodes
+    assert (p["path"], p["grid"], p["helpers"], p["fwd"]) == (PLANNED_BCR, 8, 6, FWD_BEFORE)
+    assert plan(2048, 4, D=2)["path"] == PLANNED_BCR
+    p = plan(200, 3)
+    assert (p["path"], p["grid"], p["helpers"], p["split"]) == (PLANNED_BCR, 3, 1, 0)
+    assert plan(200, 3, algo=3)["path"] == PLANNED_BCR
+    p = plan(2048, 4, tangent=0)                                   # the posterior launchers offer no fused finalize
+    assert (p["path"], p["scale_alpha"], p["scale_c"]) == (PLANNED_BCR, 1, 0)
+    assert plan(2048, 4, fin=0)["path"] == PLANNED_BCR
+    # no plan, or an algorithm that does not use it
+    p = plan(200, 3, plan=False)
+    assert (p["path"], p["grid"], p["fwd"], p["scale_alpha"], p["scale_c"]) == (BCR, 2, FWD_NOBODY, 0, 0)
+    p = plan(2048, 4, algo=2)
+    assert (p["path"], p["fwd"]) == (BCR, FWD_NOBODY)
+    p = plan(2048, 4, algo=1)
+    assert (p["path"], p["grid"], p["lds"], p["fwd"], p["scale_alpha"], p["scale_c"]) == (SWEEPS, 2, 0, FWD_NOBODY, 1, 1)
+    assert plan(200000, 4, plan=False)["path"] == SWEEPS          # auto: the chains do not fit the LDS
+    # refusals
+    assert refused(2048, 4, algo=3, plan=False) == BAD_ARG and refused(2048, 4, algo=4, plan=False) == BAD_ARG
+    assert b"asvgp_prior_plan_1d" in lib.asvgp_last_error_string()
+    assert refused(200, 3, algo=4) == UNSUPPORTED
+    assert b"matrix-core" in lib.asvgp_last_error_string()
+    assert refused(2052, 4, algo=4) == UNSUPPORTED and refused(2048, 4, algo=4, D=2) == UNSUPPORTED
+    assert refused(200000, 4, algo=2, plan=False) == LDS_CAPACITY
+    assert b"LDS" in lib.asvgp_last_error_string()
+    # the split entry points: halves on the all-GPU BCR path only; elsewhere the prior half has nothing to do and the data half runs whole
+    p = plan(200, 3, plan=False, part=1)
+    assert (p["path"], p["part"], p["grid"], p["nothing"]) == (BCR_PRIOR, 1, 1, 0)
+    p = plan(200, 3, plan=False, part=2)
+    assert (p["path"], p["part"], p["grid"], p["nothing"]) == (BCR_DATA, 2, 1, 0)
+    assert plan(2048, 4, algo=1, part=1)["nothing"] == 1
+    p = plan(2048, 4, algo=1, part=2)
+    assert (p["path"], p["part"], p["nothing"]) == (SWEEPS, 0, 0)
+    assert plan(2048, 4, part=1)["nothing"] == 1 and plan(200, 3, part=1)["nothing"] == 1
+    p = plan(2048, 4, part=2)
+    assert (p["path"], p["part"], p["nothing"], p["grid"]) == (MATRIX_CORE, 0, 0, 3)
+    p = plan(200, 3, part=2)
+    assert (p["path"], p["part"], p["nothing"]) == (PLANNED_BCR, 0, 0)
+    # who runs the forward pass of the planned Kuu chain
+    assert plan(2048, 4, defer=1)["fwd"] == FWD_CALLER
+    assert plan(2048, 4, worker=1)["fwd"] == FWD_WORKER and plan(2048, 4, worker=1, defer=1)["fwd"] == FWD_WORKER
+    assert plan(2048, 4, gpu=1)["fwd"] == FWD_GPU and plan(2048, 4, gpu=1, worker=1)["fwd"] == FWD_GPU
+    assert plan(2048, 4, plan_first=1)["fwd"] == FWD_BEFORE
+    assert plan(200, 3, gpu=1)["fwd"] == FWD_GPU and plan(200, 3, worker=1, defer=1)["fwd"] == FWD_BEFORE
+    # launch-ahead: the matrix-core launch with the host forward pass, and nothing else
+    p = plan(2048, 4, ahead=1)
+    assert (p["path"], p["fwd"], p["grid"]) == (MATRIX_CORE, FWD_PUBLISH_THETA, 3)
+    assert plan(2048, 4, ahead=1, worker=1)["fwd"] == FWD_PUBLISH_THETA and plan(2048, 4, ahead=1, defer=1)["fwd"] == FWD_PUBLISH_THETA
+    for kw in (dict(gpu=1), dict(plan_first=1)):                   # matrix-core, but not the host forward pass behind the launch
+        assert refused(2048, 4, ahead=1, **kw) == UNSUPPORTED
+        assert b"launch-ahead" in lib.asvgp_last_error_string()
+    for a, kw in (((200, 3), {}), ((2052, 4), {}), ((2048, 4), dict(D=2)),                                 # planned chain on the BCR kernel
+                  ((200, 3), dict(plan=False)), ((2048, 4), dict(algo=2)),                                # BCR
+                  ((200, 3), dict(plan=False, part=1)), ((200, 3), dict(plan=False, part=2)),             # its halves
+                  ((2048, 4), dict(algo=1)), ((200000, 4), dict(plan=False)), ((2048, 4), dict(plan=False, algo=1))):   # sweeps
+        assert plan(*a, **kw)["path"] != MATRIX_CORE
+        assert refused(*a, ahead=1, **kw) == UNSUPPORTED, (a, kw)
+        assert b"launch-ahead" in lib.asvgp_last_error_string()
+    # argument checks of the entry itself
+    assert lib.asvgp_elbo_launch_plan_host(0, 0, 0, 0, 64, 4, 1, 0, 1, 1, 0, 0, 0, 0, 0, 0, None) == BAD_ARG
+    out = np.zeros(12, dtype=np.int64)
+    assert lib.asvgp_elbo_launch_plan_host(0, 0, 0, 0, 64, 7, 1, 0, 1, 1, 0, 0, 0, 0, 0, 0, out.ctypes.data) == UNSUPPORTED
+
+
 def test_two_sided_factorisation_layout_invariants():
     """asvgp_amd.kronecker.twisted_layout (host logic of GPR_kron's two-sided band Cholesky): for every size both systems have nb super-blocks,
     the separator is their last block, paddings are non-negative, the interiors do not overlap and together with the separator cover

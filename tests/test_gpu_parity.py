@@ -1912,6 +1912,62 @@ def test_launch_ahead_of_theta_gives_the_ordinary_launch_numbers(A):
     assert np.isfinite(r3).all()
 
 
+def _small_models(A, N=2000):
+    rng = np.random.default_rng(23)
+    x = rng.uniform(1e-9, 1 - 1e-9, N)
+    y = (np.sin(20 * x) + 0.1 * rng.normal(size=N)).reshape(-1, 1)
+    out = []
+    for basis in (A.B4Spline(0, 1, 64), A.B3Spline(0, 1, 200)):
+        m = A.GPR_1d((x.reshape(-1, 1), y), A.Matern32(variance=1.0, lengthscales=0.1), basis)
+        m.likelihood.variance.assign(0.02)
+        out.append(m)
+    return out
+
+
+def test_launch_ahead_on_a_handle_that_cannot_take_it_launches_nothing(A):
+    """asvgp_elbo_grad_ahead_1d outside the matrix-core launch - band algorithm 1 or 2 on the k = 4 model, the k = 3 model under auto - is
+    ASVGP_ERR_UNSUPPORTED decided in the launch plan: launch_elbo_ahead() is None, `out` and `info` keep their bits (nothing ran at the
+    placeholder theta), no launch waits for a theta, and the handle keeps working (17 more launches: every ring slot is reused)."""
+    m4, m3 = _small_models(A)
+    for model, algos in ((m4, (1, 2)), (m3, (0,))):
+        ref = model.elbo_and_grad().cpu().numpy()
+        for algo in algos:
+            model._h.set_band_algorithm(algo)
+            model.elbo_and_grad()
+            torch.cuda.synchronize()
+            out0, info0 = model._out.clone(), model._info.clone()
+            assert model.launch_elbo_ahead() is None
+            torch.cuda.synchronize()
+            assert torch.equal(model._out.view(torch.int64), out0.view(torch.int64)) and torch.equal(model._info, info0)
+            with pytest.raises(A._lib.AsvgpError, match="no launch is waiting"):
+                model.publish_theta()
+        model._h.set_band_algorithm(0)
+        for _ in range(17):
+            got = model.elbo_and_grad().cpu().numpy()
+        np.testing.assert_allclose(got, ref, rtol=1e-12)
+        model.close()
+
+
+def test_a_refused_launch_ahead_leaks_no_table_slot(A):
+    """Launch-ahead with the forward pass on the GPU (asvgp_set_prior_forward(h, 1)) is refused in the plan, before a slot of the pinned
+    table ring is taken: 17 ordinary launches afterwards (the ring has 16 slots) and the teardown - both wait, up to 2 s, for a slot whose
+    kernel never reports - take milliseconds."""
+    model = _small_models(A)[0]
+    model._h.set_prior_forward(1)
+    ref = model.elbo_and_grad().cpu().numpy()                       # warm-up: plan image, device table ring, result mirror
+    assert model.launch_elbo_ahead() is None
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    assert model.launch_elbo_ahead() is None
+    for _ in range(17):
+        got = model.elbo_and_grad().cpu().numpy()
+    model.close()
+    elapsed = time.perf_counter() - t0
+    print("refused launch-ahead, 17 launches, close: %.4f s" % elapsed)
+    assert elapsed < 1.0
+    np.testing.assert_allclose(got, ref, rtol=1e-12)
+
+
 def test_host_result_mirror_gives_the_stream_path_numbers(A):
     """asvgp_result_mirror (include/asvgp_hip.h): the fused launch writes [out, info, sequence] into pinned host memory and the host polls
     the sequence word; the numbers are the ones the stream path returns, a launch that cannot write the mirror (band algorithm 1)
