@@ -80,6 +80,8 @@ SIGNATURES = {
     "asvgp_loo_1d": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _Z, _P]),
     "asvgp_score_workspace_bytes": (_Z, [_L, _I, _L]),
     "asvgp_score_1d": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _D, _D, _P, _P, _P, _P, _P, _Z, _P]),
+    "asvgp_weight_grad_workspace_bytes": (_Z, [_L, _I, _L, _L]),
+    "asvgp_weight_grad_1d": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _D, _I, _L, _P, _P, _P, _D, _D, _P, _L, _P, _P, _P, _Z, _P]),
     "asvgp_predict_1d": (_I, [_P, _L, _P, _L, _D, _I, _L, _P, _P, _D, _L, _P, _P, _P]),
     "asvgp_predict_1d_h": (_I, [_P, _P, _L, _P, _L, _D, _I, _L, _P, _P, _D, _L, _P, _P, _P]),
     "asvgp_posterior_cov_workspace_bytes": (_Z, [_L, _I, _L]),

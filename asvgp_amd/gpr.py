@@ -85,23 +85,36 @@ def _prepare_heldout(data, weights, ncol, D, dev, what):
     return X.contiguous(), Y.contiguous(), w
 
 
-def _prepare_folds(folds, n, weights, dev, what):
-    """Fold labels of this rank's n rows -> (int64 device tensor (n,), per-fold count of rows with positive weight (K_local,) int64).
-    ValueError for a wrong shape, a label that is not an integer, or a negative label."""
-    f = torch.as_tensor(folds)
+def _prepare_labels(labels, n, dev, what, noun):
+    """Integer labels (noun = "fold" / "group") of this rank's n rows -> int64 device tensor (n,).  ValueError, before anything is
+    launched, for a wrong shape, a label that is not an integer, or a negative label."""
+    f = torch.as_tensor(labels)
     if f.dim() == 2 and f.shape[1] == 1:
         f = f.reshape(-1)
     if f.dim() != 1 or f.shape[0] != n:
-        raise ValueError("%s: folds must have shape (N,) with N = %d rows; got %s" % (what, n, tuple(f.shape)))
+        raise ValueError("%s: %ss must have shape (N,) with N = %d rows; got %s" % (what, noun, n, tuple(f.shape)))
     if f.dtype.is_floating_point or f.dtype == torch.bool or f.dtype.is_complex:
-        raise ValueError("%s: folds must be an integer array; got %s" % (what, f.dtype))
+        raise ValueError("%s: %ss must be an integer array; got %s" % (what, noun, f.dtype))
     f = f.to(device=dev, dtype=torch.int64).contiguous()
     if n and int(f.min().item()) < 0:
         i = int(torch.nonzero(f < 0)[0].item())
-        raise ValueError("%s: folds must be >= 0; row %d has fold %d" % (what, i, int(f[i].item())))
+        raise ValueError("%s: %ss must be >= 0; row %d has %s %d" % (what, noun, i, noun, int(f[i].item())))
+    return f
+
+
+def _prepare_folds(folds, n, weights, dev, what):
+    """Fold labels of this rank's n rows -> (int64 device tensor (n,), per-fold count of rows with positive weight (K_local,) int64).
+    ValueError for a wrong shape, a label that is not an integer, or a negative label."""
+    f = _prepare_labels(folds, n, dev, what, "fold")
     pos = f if weights is None else f[weights > 0]
     counts = torch.bincount(pos, minlength=(int(f.max().item()) + 1) if n else 0)
     return f, counts
+
+
+def _prepare_groups(groups, n, dev, what):
+    """Group labels of this rank's n rows -> (int64 device tensor (n,), G_local = max + 1; 0 for no rows); validated as folds are."""
+    g = _prepare_labels(groups, n, dev, what, "group")
+    return g, (int(g.max().item()) + 1) if n else 0
 
 
 def _require_folds_populated(counts, what):
@@ -389,6 +402,106 @@ class _GPModelSurface:
         n, ld, sq, chi = (sum(s[k] for s in out) for k in ("n", "log_density", "sq_err", "chi2"))
         return dict(folds=out, total=_score_dict(n, ld, sq, chi, self.y.shape[1]))
 
+    # -- gradient of the bound in the weights, learned noise scales per group (GPR_1d, and GPR_kron with d = 2) -----------------
+    def weight_gradient_device(self):
+        self._weights_unsupported("weight_gradient_device")
+
+    def noise_group_gradient(self, groups):
+        self._weights_unsupported("noise_group_gradient")
+
+    def fit_noise_groups(self, groups, maxiter=200, pinned=0):
+        self._weights_unsupported("fit_noise_groups")
+
+    def _bound_and_grad(self):
+        """(bound as a float, its gradient in trainable_parameters as numpy): the model's analytic elbo_and_grad*"""
+        raise NotImplementedError
+
+    def _global_groups(self, groups, what):
+        """validated labels of this rank's rows and G = max + 1 (global on a sharded model)"""
+        labels, G = _prepare_groups(groups, self.X.shape[0], self._stats.device, what)
+        if self._is_sharded():
+            Gt = torch.tensor([G], dtype=torch.int64, device=labels.device)
+            dist.all_reduce(Gt, op=dist.ReduceOp.MAX, group=self._pg)
+            G = int(Gt.item())
+        if G < 1:
+            raise ValueError("%s: no rows, no groups" % what)
+        return labels, G
+
+    def _group_sums_local(self, labels, G):
+        """[n_g, T_g] (G, 2) over this rank's rows, device: index_add_ on the per-row gradient"""
+        gr = self.weight_gradient_device()
+        w = torch.ones_like(gr) if self.weights is None else self.weights
+        out = torch.zeros((G, 2), dtype=torch.float64, device=gr.device)
+        out[:, 0].index_add_(0, labels, (w > 0).to(torch.float64))
+        out[:, 1].index_add_(0, labels, w * gr)                 # (a row with weight 0 has gradient 0)
+        return out
+
+    def _group_sums(self, labels, G):
+        """[n_g, T_g] (G, 2) as numpy, global on a sharded model (SUM, as kfold_scores adds its counts)"""
+        sums = self._group_sums_local(labels, G)
+        if self._is_sharded():
+            sums = sums.clone()
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self._pg)
+        return sums.cpu().numpy()
+
+    def _noise_group_gradient(self, groups):
+        labels, G = self._global_groups(groups, "%s.noise_group_gradient" % type(self).__name__)
+        sums = self._group_sums(labels, G)
+        return dict(n=np.rint(sums[:, 0]).astype(np.int64), grad_log_weight=sums[:, 1].copy())
+
+    def _fit_noise_groups(self, groups, maxiter, pinned):
+        from scipy.optimize import minimize
+        name = "%s.fit_noise_groups" % type(self).__name__
+        if self.weights is None:
+            raise ValueError("%s: this model was built without weights (pass weights= to the constructor)" % name)
+        labels, G = self._global_groups(groups, name)
+        pinned = int(pinned)
+        if not 0 <= pinned < G:
+            raise ValueError("%s: pinned = %d is not one of the %d groups" % (name, pinned, G))
+        dev = self._stats.device
+        params = self.trainable_parameters
+        theta0 = [(p._u, p._value) for p in params]
+        nth = len(params)
+        free = np.array([g for g in range(G) if g != pinned], dtype=np.int64)
+        state = self._kfold_state()
+        w0 = state["weights"]
+
+        def log_rho(u):
+            lr = np.zeros(G)
+            lr[free] = u[nth:]
+            return lr
+
+        def apply(u):
+            """theta and the weights w0_i / rho_{g_i} of the point u"""
+            for p, ui in zip(params, u[:nth]):
+                p.unconstrained = float(ui)
+            rho = torch.as_tensor(np.exp(log_rho(u)), dtype=torch.float64, device=dev)
+            self._apply_weights(w0 / rho[labels])
+
+        def fun(u):
+            apply(u)
+            try:
+                e, g = self._bound_and_grad()
+            except NotPositiveDefiniteError:
+                return np.inf, np.zeros(len(u))
+            if not np.isfinite(e):
+                return np.inf, np.zeros(len(u))
+            T = self._group_sums(labels, G)[:, 1]               # d bound / d log rho_g = -T_g
+            grad = np.concatenate([np.asarray(g) * np.array([p.dtheta_du() for p in params]), -T[free]])
+            return -e, -grad
+
+        try:
+            u0 = np.concatenate([np.array([p.unconstrained for p in params]), np.zeros(G - 1)])
+            res = minimize(fun, u0, jac=True, method="L-BFGS-B", options=dict(maxiter=maxiter))
+            apply(res.x)
+        except BaseException:
+            for p, (u, v) in zip(params, theta0):
+                p._u, p._value = u, v
+            self._kfold_restore(state)
+            raise
+        self.noise_scales = np.exp(log_rho(res.x))
+        return res
+
     def close(self):
         """Release the model's library handle now (pinned table ring, result mirror, plan) instead of at garbage collection."""
         h = getattr(self, "_h", None)
@@ -454,6 +567,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._post = None
         self._post_loo = None                 # (theta, alpha, W, Pinv_band) of the leave-one-out methods
         self._loo_ws = self._score_ws = None  # workgroup records of asvgp_loo_1d / asvgp_score_1d (allocated on first use)
+        self._wgrad_ws = None                 # records or bin rows of asvgp_weight_grad_1d (allocated on first use, grown with G)
         self._post_cov = None                 # (theta, W_dense): the dense P^-1 - Kuu^-1 of predict_f_cov_device
         self._cov_ws = None
         self._host_result = np.zeros(10)      # [out[0..7], info[0], info[1]] of the last host-read evaluation
@@ -829,6 +943,62 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         runs on an internal weighted twin with w = 1."""
         return self._kfold_scores(folds, refit, maxiter)
 
+    # -- gradient of the bound in the weights (asvgp_weight_grad_1d; not in the reference) --------------------------------------
+    GSUM_MAX_GROUPS = 1024                    # asvgp_weight_grad_1d keeps 2 G bins per workgroup in LDS up to this G
+
+    def _weight_grad(self, want_grad, labels32=None, G=None):
+        """asvgp_weight_grad_1d over this rank's rows on _posterior_loo()'s tables: (grad (N,) or None, gsum (G, 2) or None (G = None));
+        labels32: int32 device labels, or None for the one-group fixed-order sums."""
+        b = self.basis
+        lib = get_lib()
+        dev = self._stats.device
+        n = self.X.shape[0]
+        tables = self._posterior_loo()
+        need = lib.asvgp_weight_grad_workspace_bytes(b.m, b.order, self.D, G or 1) // 8
+        if self._wgrad_ws is None or self._wgrad_ws.numel() < need:
+            self._wgrad_ws = torch.empty(need, dtype=torch.float64, device=dev)
+        ws = self._wgrad_ws
+        grad = torch.empty(n, dtype=torch.float64, device=dev) if want_grad else None
+        gsum = torch.empty((G, 2), dtype=torch.float64, device=dev) if G else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        check(lib.asvgp_weight_grad_1d(self._h.ptr, self.X.data_ptr(), self.y.data_ptr(), ptr(self.weights), n, self.D, b.mesh.data_ptr(),
+                                       b.mesh.shape[0], b.delta_np, b.order, b.m, *[t.data_ptr() for t in tables],
+                                       float(self.kernel.variance), float(self.likelihood.variance), ptr(labels32), G or 1, ptr(grad),
+                                       ptr(gsum), ws.data_ptr(), ws.numel() * 8, stream_ptr()), "weight_grad_1d")
+        return grad, gsum
+
+    def weight_gradient_device(self):
+        """d ELBO_w / d w_i (N,) over this rank's rows as a device tensor (include/asvgp_hip.h: 1/2 [D / w_i - (D g_i + sum_d r_id^2 +
+        var_i - g_i) / sigma2]; 0 for a row with weight 0): one streaming kernel on the leave-one-out tables.  A model built without
+        weights is the model with w = 1."""
+        return self._weight_grad(True)[0]
+
+    def _group_sums_local(self, labels, G):
+        if G > self.GSUM_MAX_GROUPS:
+            return super()._group_sums_local(labels, G)
+        return self._weight_grad(False, None if G == 1 else labels.to(torch.int32), G)[1]
+
+    def noise_group_gradient(self, groups):
+        """groups: int array (N,) over this rank's rows with values >= 0 (G = max + 1, global on a sharded model).  Returns
+        dict(n (G,) int64, grad_log_weight (G,)) as numpy: n_g counts the rows of group g with w_i > 0 and grad_log_weight[g] =
+        T_g = sum_{i in g} w_i d ELBO_w / d w_i is the derivative of the bound in the log of a common factor on the group's weights - the
+        derivative in the log of the group's NOISE scale is -T_g.  Nothing of size N is written up to G = 1024 (the kernel's own bins);
+        above that the per-row gradient is summed with index_add_.  On a sharded model the sums are all-reduced with SUM."""
+        return self._noise_group_gradient(groups)
+
+    def fit_noise_groups(self, groups, maxiter=200, pinned=0):
+        """Fit the relative noise scales of the G groups together with the model's parameters: row i gets the weight w0_i / rho_{g_i} (w0:
+        the weights at the call, so its noise variance is sigma2 rho_g / w0_i) and L-BFGS-B maximises the bound in trainable_parameters
+        and log rho_g, g != pinned.  rho_pinned = 1: sigma2 carries the common scale, since scaling every weight by c is scaling sigma2
+        by 1 / c.  Every evaluation is one weighted Phi pass, the analytic elbo_and_grad and -T_g of noise_group_gradient.  On return the
+        model keeps the fitted weights and theta, noise_scales is rho (G,), and the scipy result is returned; on an exception the weights,
+        statistics, weight sums and theta are the ones at the call, bit for bit.  A model built without weights= raises ValueError."""
+        return self._fit_noise_groups(groups, maxiter, pinned)
+
+    def _bound_and_grad(self):
+        r = self.elbo_and_grad_host()
+        return r[0], np.array(r[1:4])
+
     # -- full posterior covariance (not in the reference: its predict_f(full_cov=True) raises, gpr.py:113) ------------
     def _posterior_cov(self):
         """asvgp_posterior_cov_prepare_1d once per theta: W_dense = P^-1 - Kuu^-1 (M x M, device), cached beside _post."""
@@ -954,7 +1124,7 @@ class GPR_1d(_GPModelSurface, _ShardedStats):
         self._post_cov = None
         self._post_loo = None
         self._cov_ws = None
-        self._loo_ws = self._score_ws = None
+        self._loo_ws = self._score_ws = self._wgrad_ws = None
         super().close()
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False, batch=False):
@@ -1939,16 +2109,55 @@ class GPR_kron(_GPModelSurface, _ShardedStats):
             self._weights_unsupported("kfold_scores")
         return self._kfold_scores(folds, refit, maxiter)
 
+    def _training_moments(self):
+        """_point_moments at this rank's training rows, on the factor and selected inverse of the current theta and layout"""
+        key, lay = self.theta(), self._twist_layout()
+        if self._post is None or self._post[0] != key or self._post[1].get("twist") != lay:
+            f = self._factor(want_alpha=False)
+            self._post = (key, f, self._selinv(f))               # (also fills f["alpha"])
+        return self._point_moments(self.X)
+
+    # -- gradient of the bound in the weights (d = 2), composed in torch from the per-point kernels as _loo is ----------------------
+    def weight_gradient_device(self):
+        """GPR_1d.weight_gradient_device for the d = 2 model (D = 1): 1/2 [1 / w_i - (r_i^2 + var_i) / sigma2] with
+        var_i = prod v - phi_i^T Kuu^-1 phi_i + g_i; 0 for a row with weight 0."""
+        if self._dense_mode:
+            self._weights_unsupported("weight_gradient_device")
+        mu, qk, g = self._training_moments()
+        s = float(self.likelihood.variance)
+        vprod = 1.0
+        for kern in self.kernels:
+            vprod *= float(kern.variance)
+        r = self.y.reshape(-1) - mu
+        tail = (g + r * r + (vprod - qk)) / s
+        if self.weights is None:
+            return 0.5 * (1.0 - tail)
+        w = self.weights
+        pos = w > 0
+        return torch.where(pos, 0.5 * (1.0 / torch.where(pos, w, torch.ones_like(w)) - tail), torch.zeros_like(w))
+
+    def noise_group_gradient(self, groups):
+        """GPR_1d.noise_group_gradient for the d = 2 model: index_add_ on the per-row gradient."""
+        if self._dense_mode:
+            self._weights_unsupported("noise_group_gradient")
+        return self._noise_group_gradient(groups)
+
+    def fit_noise_groups(self, groups, maxiter=200, pinned=0):
+        """GPR_1d.fit_noise_groups for the d = 2 model (same arguments, same result, same guarantees)."""
+        if self._dense_mode:
+            self._weights_unsupported("fit_noise_groups")
+        return self._fit_noise_groups(groups, maxiter, pinned)
+
+    def _bound_and_grad(self):
+        e, g = self.elbo_and_grad()
+        return float(e), g
+
     # -- leave-one-out predictions in closed form (d = 2; not in the reference) ------------------------------------------------
     def _loo(self):
         """The formulas of asvgp_loo_1d (include/asvgp_hip.h) in torch on the device, over this rank's rows, from the existing per-point
         kernels: asvgp_predict_kron2d gives mu and q_K, asvgp_predict_kron2d_var (or its twisted form, whichever layout _twist_layout()
         chose) gives g.  Returns (mean (N, 1), var (N, 1), logdens (N,), h (N,), pos (N,) bool); nothing is clamped."""
-        key, lay = self.theta(), self._twist_layout()
-        if self._post is None or self._post[0] != key or self._post[1].get("twist") != lay:
-            f = self._factor(want_alpha=False)
-            self._post = (key, f, self._selinv(f))               # (also fills f["alpha"])
-        mu, qk, g = self._point_moments(self.X)
+        mu, qk, g = self._training_moments()
         s = float(self.likelihood.variance)
         vprod = 1.0
         for kern in self.kernels:

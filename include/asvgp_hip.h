@@ -488,7 +488,41 @@ int asvgp_score_1d(asvgp_handle_t handle, const double* x, const double* y, cons
                    size_t workspace_bytes, asvgp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * 2-D Kronecker (tensor-product) path  replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
+ * Gradient of the weighted bound in the weights (GPR_1d.weight_gradient_device / noise_group_gradient / fit_noise_groups; not in the
+ * reference).  With the notation of "Per-observation noise weights" and of the leave-one-out block above (s = sigma2, r_id = y_id - mu_id,
+ * g_i = phi_i^T P^-1 phi_i, var_i = variance + phi_i^T W phi_i, so var_i - g_i = variance - phi_i^T Kuu^-1 phi_i):
+ *   d ELBO_w / d w_i = 1/2 [ D / w_i - D g_i / s - sum_d r_id^2 / s - (var_i - g_i) / s ]        (w_i > 0)
+ * (D = 1: 1/2 [1 / w_i - (r_i^2 + var_i) / s]; for D > 1 the bound counts the trace terms once, so D g_i does not cancel).  Scaling every
+ * weight by c is scaling s by 1 / c: sum_i w_i d ELBO_w / d w_i = -s d ELBO_w / d s, which asvgp_elbo_grad_1d returns.
+ * x, y, w (or NULL: all ones), alpha, W, Pinv_band, variance, noise variance: as asvgp_loo_1d takes them.  groups: N int32 labels on the
+ * device, or NULL, which requires G = 1.  Outputs, each nullable, at least one asked for:
+ *   grad (N): the derivative above; 0 for a row with w_i = 0, which is absent from the model.
+ *   gsum (G x 2, overwritten): [n_g = #{i in g, w_i > 0}, T_g = sum_{i in g, w_i > 0} w_i d ELBO_w / d w_i].  T_g is the derivative of the
+ *   bound in the log of a common factor on the weights of group g; the derivative in the log of the group's noise scale is -T_g.
+ * A third mode of asvgp_loo_1d's kernel, by the same plan (orders 1..6, any M, D >= 1, any 8-byte alignment, any row order): W and
+ * band(P^-1) interleaved in LDS from N = 65 536 on, up to 4 ranges of mesh cells (2 for orders 5 and 6), else the tables through the
+ * caches; a grid of at most 262 144 threads per range.  24 B read per row (16 B unweighted) and range, + 4 B for a label; 8 B written
+ * with grad, nothing of size N without.
+ * groups = NULL: n and T go through asvgp_loo_1d's fixed-order reduction (per wavefront, per workgroup record, a one-wavefront launch):
+ * the same call made twice returns the same bits.  With groups every workgroup keeps 2 G bins in LDS (16 G bytes, counted against the
+ * staged plan's LDS budget: with G = 1024, k = 4, D = 1 the tables stay whole up to M = 1525), adds its rows to them with LDS atomics,
+ * stores them as one row of the workspace (at most 1024 rows of 2 G doubles), and a second small kernel adds the rows in a fixed
+ * order (sixteen interleaved slices of the rows, each in workgroup order, then the slices in index order).  No floating-point atomics to global memory.  n_g is exact; T_g is reproducible to rounding only (the order of the LDS adds
+ * inside a workgroup is not fixed).  A label outside [0, G) never indexes memory: its row is left out of gsum (grad still gets it).
+ * N = 0: ASVGP_OK, nothing launched, gsum zeroed.  Return codes and argument rules are asvgp_loo_1d's, and: ASVGP_ERR_BAD_ARG for G < 1,
+ * for groups = NULL with G != 1 or for grad and gsum both NULL; ASVGP_ERR_UNSUPPORTED for G > 1024; ASVGP_ERR_WORKSPACE for a workspace
+ * shorter than asvgp_weight_grad_workspace_bytes (0 for arguments the entry refuses).  The handle may be NULL.
+ * Measured (tools/weight_grad_probe.py, one MI355X, N = 10M unsorted rows, M = 2048, k = 4, D = 1, weighted): grad 251 us; gsum only
+ * 177 us (G = 1), 191 us (G = 16), 187 us (G = 1024); asvgp_loo_1d's scores-only pass over the same bytes 279 us in the same process.
+ * ---------------------------------------------------------------------------------------------- */
+size_t asvgp_weight_grad_workspace_bytes(int64_t M, int order, int64_t D, int64_t G);
+int asvgp_weight_grad_1d(asvgp_handle_t handle, const double* x, const double* y, const double* w, int64_t N, int64_t D,
+                         const double* mesh, int64_t n_mesh, double delta, int order, int64_t M, const double* alpha, const double* W,
+                         const double* Pinv_band, double variance, double noise_variance, const int32_t* groups, int64_t G, double* grad,
+                         double* gsum, void* workspace, size_t workspace_bytes, asvgp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2-D Kronecker (tensor-product) path replaces kronecker.make_kvs_sparse kronecker.py:7-33 and the dense
  * linear algebra of GPR_kron gpr.py:239-359 (KufKfu.todense(), tf.linalg.cholesky / triangular_solve / cholesky_solve).
  * Basis pair (i1, i2) has row index i1*m2 + i2 (dim-0 major, as make_kvs_two_sparse).  Both bases share `order` = k
  * (gpr.py:261 takes bases[0].order).  X: (N, 2) row-major, 16-byte aligned.
