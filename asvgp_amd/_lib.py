@@ -43,6 +43,7 @@ SIGNATURES = {
     "asvgp_set_phi_workgroups": (_I, [_P, _I]),
     "asvgp_set_phi_deferred_reduce": (_I, [_P, _I]),
     "asvgp_phi_reduce_1d": (_I, [_P, _P]),
+    "asvgp_phi_launch_plan_host": (_I, [_I, _I, _I, _I, _L, _L, _L, _I, _L, _D, _I, _I, _D, _D, _I, _P]),
     "asvgp_phi_index_1d": (_I, [_P, _L, _P, _L, _D, _P, _P]),
     "asvgp_phi_evaluate_1d": (_I, [_P, _L, _P, _L, _D, _I, _I, _P, _P, _P]),
     "asvgp_matern_coeffs": (_I, [_I, _D, _D, _c.POINTER(_D), _c.POINTER(_D), _c.POINTER(_I)]),

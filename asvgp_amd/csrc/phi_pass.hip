@@ -686,64 +686,9 @@ __global__ __launch_bounds__(1024) void predict_poly_kernel(const double* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side
+// host side (the Phi pass's own - plan, launchers, C entries - is phi_launch.hpp, included at the end of this file)
 // ---------------------------------------------------------------------------------------------
-static int phi_max_cols(int K, long n_mesh, bool fx) {
-  long avail = (long)PHI_LDS_BUDGET - (long)n_mesh * 8 - 16 * 8;
-  if (avail <= 0) return 0;
-  return (int)(avail / (8 * (K + 2 + (fx ? 1 : 0))));
-}
-
-// Centred-moment Phi pass (algorithm 5, phi_moments.hpp).  Returns 1 when it does not apply (D != 1, unaligned inputs, or the
-// image does not fit the LDS at this M) and the caller falls back to the band-scatter kernel.
-template <int K, int CS>
-static int launch_phi_moments_cs(Handle* h, const double* x, const double* y, long N, const double* mesh, long n_mesh, double delta,
-                                 long M, double* stats, double* ws, hipStream_t st, bool regular, double step) {
-  const int ncells = (int)n_mesh - 1;
-  const size_t lds_bytes = mq_lds_bytes<K, CS>(M);
-  if (ncells > CS || lds_bytes > PHI_LDS_BUDGET) return 1;
-  long nblk = (N + 2 * MQ_THREADS - 1) / (2 * MQ_THREADS);
-  const long gmax = (h->phi_blocks > 0 && h->phi_blocks < PHI_MAX_BLOCKS) ? h->phi_blocks : PHI_MAX_BLOCKS;
-  const int G = (int)(nblk < 1 ? 1 : (nblk > gmax ? gmax : nblk));
-  long ppb = (N + G - 1) / G;
-  ppb = ((ppb + 2 * MQ_THREADS - 1) / (2 * MQ_THREADS)) * (2 * MQ_THREADS);
-  int s0 = 50;   // 62 - ceil(log2(points per workgroup)), at most 50 (magic-constant conversion range)
-  { long c = 2; int lg = 1; while (c < ppb) { c <<= 1; ++lg; } if (62 - lg < s0) s0 = 62 - lg; }
-  MqArgs a;
-  a.x = x; a.y = y; a.N = N; a.mesh_g = mesh; a.n_mesh = (int)n_mesh; a.inv_delta = 1.0 / delta; a.M = (int)M; a.step = step;
-  a.partials = ws;
-  a.ov = ws + (size_t)PHI_MAX_BLOCKS * ((size_t)(K + 2) * M + 1);
-  a.ppb = ppb; a.zero_ptr = stats; a.zero_n = (K + 2) * M + 1; a.s0 = s0;
-  auto kern = regular ? phi_moment_kernel<K, CS, true> : phi_moment_kernel<K, CS, false>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) { set_error("hipFuncSetAttribute(%zu B LDS): %s", lds_bytes, hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-  const bool prof = h->prof_on && h->prof_n < PROF_RING && (h->prof_calls++ % h->prof_every == 0);
-  if (prof) (void)hipEventRecord(h->prof_ev[h->prof_n][0], st);
-  hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(MQ_THREADS), lds_bytes, st, a);
-  if (prof) { (void)hipEventRecord(h->prof_ev[h->prof_n][1], st); ++h->prof_n; }
-  const int E1 = (int)((K + 2) * M + 1);
-  const int gsplit = G >= 64 ? 16 : (G >= 8 ? 4 : 1);
-  if (h->phi_defer) {   // the caller enqueues the reduce itself (asvgp_phi_reduce_1d), e.g. on the stream that consumes the statistics
-    h->pend = Handle::PendingReduce{a.partials, G, (int)M, K, stats, true, nullptr};
-    return check_launch("phi_accumulate_1d (moments, reduce deferred)");
-  }
-  hipLaunchKernelGGL(phi_reduce_kernel, dim3((E1 + 255) / 256, gsplit), dim3(256), 0, st, a.partials, G, (int)M, K, 0, M, 1L, 0, 1, stats, (const int*)nullptr);
-  return check_launch("phi_accumulate_1d (moments)");
-}
-
-template <int K>
-static int launch_phi_moments(Handle* h, const double* x, const double* y, long N, long D, const double* mesh, long n_mesh, double delta,
-                              long M, double* stats, double* ws, hipStream_t st) {
-  if (D != 1 || N < 1 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) != 0) return 1;
-  double step = 0.0;
-  const bool regular = handle_mesh_is_linspace(h, mesh, n_mesh, st, &step, nullptr, nullptr);
-  int rc = launch_phi_moments_cs<K, 512>(h, x, y, N, mesh, n_mesh, delta, M, stats, ws, st, regular, step);     // plane stride: smallest that holds the cells
-  if (rc == 1) rc = launch_phi_moments_cs<K, 1024>(h, x, y, N, mesh, n_mesh, delta, M, stats, ws, st, regular, step);
-  if (rc == 1) rc = launch_phi_moments_cs<K, 2048>(h, x, y, N, mesh, n_mesh, delta, M, stats, ws, st, regular, step);
-  return rc;
-}
-
-// Input-order probe: rows of 128 consecutive points, one per lane pair as the kernels read them; a row conforms when its points lie in
+// Input-order probe (launched by handle_phi_is_series, phi_launch.hpp): rows of 128 consecutive points, one per lane pair as the kernels read them; a row conforms when its points lie in
 // at most two mesh cells (the arithmetic cell guess, spread <= 2 as in the kernel's own first vote).  count += conforming rows.
 __global__ __launch_bounds__(64) void phi_order_probe_kernel(const double* __restrict__ x, long N, long row_stride, int nrows_probe, double m0, double inv_delta,
                                                              int n_mesh, int* __restrict__ count) {
@@ -763,195 +708,9 @@ __global__ __launch_bounds__(64) void phi_order_probe_kernel(const double* __res
   if (lane == 0 && good) atomicAdd(count, 1);
 }
 
-// Is x a time series (sorted / locally sorted)?  Decided once per (pointer, N) from 512 sampled rows; a stale verdict - the caller has
-// overwritten the buffer with data of another order - costs speed, never correctness.
-static bool handle_phi_is_series(Handle* h, const double* x, long N, double m0, double inv_delta, long n_mesh, hipStream_t st) {
-  if (h->phi_order == 1) return false;
-  if (h->phi_order == 2) return true;
-  for (int i = 0; i < h->n_order_seen; ++i)
-    if (h->order_seen[i].ptr == x && h->order_seen[i].n == N) return h->order_seen[i].series != 0;
-  int series = 0;
-  const int nprobe = 512;
-  if (N >= 128L * nprobe) {
-    if (!h->order_dev && hipMalloc(&h->order_dev, sizeof(int)) != hipSuccess) h->order_dev = nullptr;
-    int cnt = 0;
-    if (h->order_dev && hipMemsetAsync(h->order_dev, 0, sizeof(int), st) == hipSuccess) {
-      hipLaunchKernelGGL(phi_order_probe_kernel, dim3(nprobe), dim3(64), 0, st, x, N, N / nprobe, nprobe, m0, inv_delta, (int)n_mesh, h->order_dev);
-      if (hipMemcpyAsync(&cnt, h->order_dev, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
-        series = cnt * 10 >= nprobe * 9 ? 1 : 0;                 // nine rows in ten: the front loop will carry the pass
-    }
-  }
-  if (h->n_order_seen < 8) h->order_seen[h->n_order_seen++] = Handle::OrderSeen{x, N, series};
-  return series != 0;
-}
-
-// Tile-sort Phi pass (algorithm 6, phi_sort.hpp).  Returns 1 when it does not apply - D != 1, unaligned inputs, fewer than two points,
-// more than 2048 columns, a mesh that is not an exact numpy.linspace, or knots so large against delta that the arithmetic cell guess
-// has no safe margin - and the caller falls back to the moment scatter (5), then the band scatter (3).
-// Two instantiations: TP points per thread and tile without the time-series front loop (fastest on i.i.d. points), and 4 points per
-// thread and tile with it (TS; the run sums and the second register set of its prefetch need the room) for inputs the order probe
-// - or the caller, asvgp_set_phi_input_order - calls a time series.
-template <int K, int TP, int TS>
-static int launch_phi_sort_as(Handle* h, const double* x, const double* y, long N, const double* mesh, long n_mesh, double delta,
-                              long M, double* stats, double* ws, hipStream_t st, double step, double m0, double m_last, double margin) {
-  size_t lds_bytes = ps_lds_bytes<K, TP, TS>();
-  if (ps_epilogue_bytes<K>() > lds_bytes) lds_bytes = ps_epilogue_bytes<K>();
-  if (lds_bytes > 160 * 1024) return 1;
-  long nblk = (N + TP * PS_THREADS - 1) / (TP * PS_THREADS);   // at least one tile per workgroup
-  const long gmax = (h->phi_blocks > 0 && h->phi_blocks < PHI_MAX_BLOCKS) ? h->phi_blocks : PHI_MAX_BLOCKS;
-  const int G = (int)(nblk < 1 ? 1 : (nblk > gmax ? gmax : nblk));
-  long ppb = (N + G - 1) / G;
-  ppb = TS ? ((ppb + 127) & ~127L) : ((ppb + 1) & ~1L);       // (TS: whole rows of 64 pairs - only the grid's last workgroup has an incomplete one)
-  if (ppb > 0x3fffffffL) return 1;                              // (32-bit pair indices inside a workgroup)
-  PsArgs a;
-  a.x = x; a.y = y; a.N = N; a.mesh_g = mesh; a.n_mesh = (int)n_mesh; a.inv_delta = 1.0 / delta; a.M = (int)M;
-  a.m0 = m0; a.m_last = m_last; a.step = step; a.smax_fast = 0.5 - margin;
-  a.partials = ws; a.ppb = ppb; a.zero_ptr = stats; a.zero_n = (K + 2) * M + 1; a.stamps = nullptr; a.stamps_wave = 0;
-  a.ranges = reinterpret_cast<int*>(ws + (size_t)PHI_MAX_BLOCKS * ((size_t)(K + 2) * M + 1));   // (behind the 256 partials: the moment kernel's overflow planes' room)
-  auto kern = phi_sort_kernel<K, TP, 0, 1, TS>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) { set_error("hipFuncSetAttribute(%zu B LDS): %s", lds_bytes, hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-  const bool prof = h->prof_on && h->prof_n < PROF_RING && (h->prof_calls++ % h->prof_every == 0);
-  if (prof) (void)hipEventRecord(h->prof_ev[h->prof_n][0], st);
-  hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(PS_THREADS), lds_bytes, st, a);
-  if (prof) { (void)hipEventRecord(h->prof_ev[h->prof_n][1], st); ++h->prof_n; }
-  h->phi_last_series = TS;
-  const int E1 = (int)((K + 2) * M + 1);
-  const int gsplit = G >= 64 ? 16 : (G >= 8 ? 4 : 1);
-  if (h->phi_defer) {   // the caller enqueues the reduce itself (asvgp_phi_reduce_1d), e.g. on the stream that consumes the statistics
-    h->pend = Handle::PendingReduce{a.partials, G, (int)M, K, stats, true, a.ranges};
-    return check_launch("phi_accumulate_1d (tile sort, reduce deferred)");
-  }
-  hipLaunchKernelGGL(phi_reduce_kernel, dim3((E1 + 255) / 256, gsplit), dim3(256), 0, st, a.partials, G, (int)M, K, 0, M, 1L, 0, 1, stats, (const int*)a.ranges);
-  return check_launch("phi_accumulate_1d (tile sort)");
-}
-
-template <int K>
-static int launch_phi_sort(Handle* h, const double* x, const double* y, long N, long D, const double* mesh, long n_mesh, double delta,
-                           long M, double* stats, double* ws, hipStream_t st) {
-  if (D != 1 || N < 2 || M > PS_NCELL || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) != 0) return 1;
-  double step = 0.0, m0 = 0.0, m_last = 0.0;
-  if (!handle_mesh_is_linspace(h, mesh, n_mesh, st, &step, &m0, &m_last)) return 1;
-  const double amax = fabs(m0) > fabs(m_last) ? fabs(m0) : fabs(m_last);
-  const double margin = 16.0 * 2.220446049250313e-16 * amax / delta + 1e-12;   // knot rounding (two roundings <= ulp(|knot|)) over delta
-  if (!(margin < 0.125)) return 1;
-  constexpr int TP = ps_tile_points<K>();
-  constexpr int TPS = TP < 4 ? TP : 4;
-  if (handle_phi_is_series(h, x, N, m0, 1.0 / delta, n_mesh, st)) {
-    const int rc = launch_phi_sort_as<K, TPS, 1>(h, x, y, N, mesh, n_mesh, delta, M, stats, ws, st, step, m0, m_last, margin);
-    if (rc != 1) return rc;
-  }
-  return launch_phi_sort_as<K, TP, 0>(h, x, y, N, mesh, n_mesh, delta, M, stats, ws, st, step, m0, m_last, margin);
-}
-
-// Band-scatter Phi pass (algorithms 1 and 3): the (k+1)(k+2)/2 + (k+1) products of every point go straight into the
-// workgroup's LDS band image.  Timing events (Handle::prof_*) are recorded on the launch stream right around the kernel.
-template <int K>
-static int launch_phi(Handle* h, const double* x, const double* y, long N, long D, const double* mesh, long n_mesh,
-                      double delta, long M, double* stats, double* partials, hipStream_t st) {
-  // a reduce still parked on this handle (deferred mode, e.g. the per-dimension calls of an additive model share one handle and one
-  // partials workspace) goes out now, stream-ordered before this pass overwrites the partials
-  { const int rcf = handle_flush_phi_reduce(h, nullptr, st); if (rcf) return rcf; }
-  const int ncells = (int)n_mesh - 1;
-  if (h->phi_algo == 0 || h->phi_algo == 6) {
-    const int rc = launch_phi_sort<K>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, partials, st);
-    if (rc != 1) { h->phi_last = 6; return rc; }
-    if (h->phi_algo == 6) { set_error("phi algorithm 6 (tile sort) needs D == 1, N >= 2, M <= 2048, 16-byte aligned x / y and a mesh that is an exact linspace"); return ASVGP_ERR_UNSUPPORTED; }
-  }
-  if (h->phi_algo == 0 || h->phi_algo == 5) {
-    const int rc = launch_phi_moments<K>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, partials, st);
-    if (rc != 1) { h->phi_last = 5; return rc; }
-    if (h->phi_algo == 5) { set_error("phi algorithm 5 (centred moments) needs D == 1, 16-byte aligned x / y and M small enough for the LDS split"); return ASVGP_ERR_UNSUPPORTED; }
-  }
-  const bool fx = (h->phi_algo != 1);
-  h->phi_last = fx ? 3 : 1;
-  int maxc = phi_max_cols(K, n_mesh, fx);
-  if (maxc < 2 * K + 2) {
-    set_error("phi_accumulate_1d: mesh table (%ld knots) leaves no LDS for the band", n_mesh);
-    return ASVGP_ERR_LDS_CAPACITY;
-  }
-  int cells_per_chunk = (M <= maxc) ? ncells : (maxc - K);
-  long nblk = (N + 2 * PHI_THREADS - 1) / (2 * PHI_THREADS);
-  const long gmax = (h->phi_blocks > 0 && h->phi_blocks < PHI_MAX_BLOCKS) ? h->phi_blocks : PHI_MAX_BLOCKS;
-  int G = (int)(nblk < 1 ? 1 : (nblk > gmax ? gmax : nblk));
-  long ppb = (N + G - 1) / G;
-  ppb = ((ppb + 2 * PHI_THREADS - 1) / (2 * PHI_THREADS)) * (2 * PHI_THREADS);
-  const double inv_delta = 1.0 / delta;
-  hipError_t e = hipSuccess;
-  const long zero_n = (K + 1) * M + M * D + 1;
-  bool zeroed = false;   // the first launched kernel zeroes the stats buffer
-  for (long dcol = 0; dcol < D; ++dcol) {
-    const double* yd = y + dcol;
-    bool vec = (D == 1) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && ((reinterpret_cast<uintptr_t>(yd) & 15) == 0);
-    for (int cell0 = 0; cell0 < ncells; cell0 += cells_per_chunk) {
-      int cell1 = cell0 + cells_per_chunk;
-      if (cell1 > ncells) cell1 = ncells;
-      int ncols = cell1 - cell0 + K;
-      size_t lds_bytes = sizeof(double) * ((size_t)(K + 2 + (fx ? 1 : 0)) * ncols + n_mesh + 16);
-      int do_band = (dcol == 0);
-      auto kern = fx ? (vec ? phi_accumulate_kernel<K, true, true> : phi_accumulate_kernel<K, false, true>)
-                     : (vec ? phi_accumulate_kernel<K, true, false> : phi_accumulate_kernel<K, false, false>);
-      int s0 = 50;   // 62 - ceil(log2(points per workgroup)), at most 50 (magic-constant conversion range)
-      { long c = 2; int lg = 1; while (c < ppb) { c <<= 1; ++lg; } if (62 - lg < s0) s0 = 62 - lg; }
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_bytes);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute(%zu B LDS): %s", lds_bytes, hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-      const bool prof = h->prof_on && h->prof_n < PROF_RING && (h->prof_calls++ % h->prof_every == 0);
-      if (prof) (void)hipEventRecord(h->prof_ev[h->prof_n][0], st);
-      hipLaunchKernelGGL(kern, dim3(G), dim3(PHI_THREADS), lds_bytes, st, x, yd, (long)D, N, mesh, (int)n_mesh,
-                         inv_delta, cell0, cell1, ncols, do_band, partials, ppb, zeroed ? (double*)nullptr : stats, zero_n, s0);
-      zeroed = true;
-      if (prof) { (void)hipEventRecord(h->prof_ev[h->prof_n][1], st); ++h->prof_n; }
-      int E1 = (K + 2) * ncols + 1;
-      int gsplit = G >= 64 ? 16 : (G >= 8 ? 4 : 1);
-      hipLaunchKernelGGL(phi_reduce_kernel, dim3((E1 + 255) / 256, gsplit), dim3(256), 0, st, partials, G, ncols, K,
-                         cell0, M, D, (int)dcol, do_band, stats, (const int*)nullptr);
-    }
-  }
-  return check_launch("phi_accumulate_1d");
-}
-
 }  // namespace asvgp
 
 using namespace asvgp;
-
-extern "C" size_t asvgp_phi_workspace_bytes(int64_t M, int order, int64_t D) {
-  (void)D;
-  if (M <= 0 || order < 1 || order > ASVGP_MAX_ORDER) return 0;
-  // 256 partial [band | Phi y | y^T y] images; the centred-moment kernel adds a per-workgroup fp64 plane for out-of-scale y
-  const size_t band = (size_t)PHI_MAX_BLOCKS * ((size_t)(order + 2) * (size_t)M + 1);
-  const size_t mom = band + (size_t)PHI_MAX_BLOCKS * (size_t)M;   // + the per-workgroup fp64 plane for out-of-scale y
-  return sizeof(double) * (band > mom ? band : mom);
-}
-
-extern "C" int asvgp_phi_accumulate_1d(asvgp_handle_t handle, const double* x, const double* y, int64_t N, int64_t D, const double* mesh,
-                                       int64_t n_mesh, double delta, int order, int64_t M, double* stats,
-                                       void* workspace, size_t workspace_bytes, asvgp_stream_t stream) {
-  if (((!x || !y) && N > 0) || !mesh || !stats || N < 0 || D < 1 || M < 1 || !(delta > 0.0)) {
-    set_error("phi_accumulate_1d: bad argument");
-    return ASVGP_ERR_BAD_ARG;
-  }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("phi_accumulate_1d: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  if (n_mesh != M - order + 1 || n_mesh < 2) { set_error("phi_accumulate_1d: n_mesh=%ld != M-order+1", (long)n_mesh); return ASVGP_ERR_BAD_ARG; }
-  if (M > 0x3fffffff) { set_error("phi_accumulate_1d: M too large"); return ASVGP_ERR_UNSUPPORTED; }
-  if (!workspace || workspace_bytes < asvgp_phi_workspace_bytes(M, order, D)) {
-    set_error("phi_accumulate_1d: workspace too small (%zu < %zu)", workspace_bytes, asvgp_phi_workspace_bytes(M, order, D));
-    return ASVGP_ERR_WORKSPACE;
-  }
-  hipStream_t st = as_stream(stream);
-  Handle* h = as_handle(handle);
-  double* part = static_cast<double*>(workspace);
-  switch (order) {
-    case 1: return launch_phi<1>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, part, st);
-    case 2: return launch_phi<2>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, part, st);
-    case 3: return launch_phi<3>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, part, st);
-    case 4: return launch_phi<4>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, part, st);
-    case 5: return launch_phi<5>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, part, st);
-    default: return launch_phi<6>(h, x, y, N, D, mesh, n_mesh, delta, M, stats, part, st);
-  }
-}
-
-extern "C" int asvgp_phi_last_algorithm(asvgp_handle_t handle) { return as_handle(handle)->phi_last; }
 
 // Read-only stream of x and y with the Phi pass's launch shape (one 1024-thread workgroup per CU, 16-byte loads, two per array in
 // flight per lane): the measured ceiling the Phi kernel's roofline fraction is quoted beside.  sink: >= 8 bytes, never written
@@ -992,23 +751,6 @@ extern "C" int asvgp_stream_probe(const double* x, const double* y, int64_t N, d
   ppb = (ppb + 1) & ~1L;
   hipLaunchKernelGGL(stream_probe_kernel, dim3(G), dim3(1024), 0, as_stream(stream), x, y, (long)N, ppb, sink);
   return check_launch("stream_probe");
-}
-
-namespace asvgp {
-int handle_flush_phi_reduce(Handle* h, const double* stats, hipStream_t st) {
-  if (!h->pend.valid) return ASVGP_OK;                 // nothing deferred (the accumulate call has reduced already)
-  if (stats && stats != h->pend.stats) return ASVGP_OK;
-  const Handle::PendingReduce p = h->pend;
-  h->pend.valid = false;
-  const int E1 = (p.K + 2) * p.M + 1;
-  const int gsplit = p.G >= 64 ? 16 : (p.G >= 8 ? 4 : 1);
-  hipLaunchKernelGGL(phi_reduce_kernel, dim3((E1 + 255) / 256, gsplit), dim3(256), 0, st, p.partials, p.G, p.M, p.K, 0, (long)p.M, 1L, 0, 1, p.stats, p.ranges);
-  return check_launch("phi_reduce_1d");
-}
-}  // namespace asvgp
-
-extern "C" int asvgp_phi_reduce_1d(asvgp_handle_t handle, asvgp_stream_t stream) {
-  return handle_flush_phi_reduce(as_handle(handle), nullptr, as_stream(stream));
 }
 
 extern "C" int asvgp_phi_index_1d(const double* x, int64_t N, const double* mesh, int64_t n_mesh, double delta,
@@ -1160,3 +902,4 @@ extern "C" int asvgp_predict_deriv_1d(asvgp_handle_t handle, const double* xnew,
 }
 
 #include "phi_weighted.hpp"
+#include "phi_launch.hpp"

@@ -1,7 +1,8 @@
 // Weighted Phi pass: the banded sufficient statistics of observations with per-row noise variance s / w_i,
 //   A_w = Phi W Phi^T,  b_w = Phi W y,  yy_w = sum w_i y_i^2,   wstats = [sum w, sum_{w>0} log w, #{w > 0}].
 // (included by phi_pass.hip behind the unweighted kernels, whose code it does not touch; it shares phi_reduce_kernel and the packed
-// [band | Phi y | y^T y] layout, so every consumer of `stats` is served as it is.)
+// [band | Phi y | y^T y] layout, so every consumer of `stats` is served as it is.  Kernels only: the launch rules and the C entry are
+// in phi_launch.hpp, next to the unweighted ones.)
 //
 // Two kernels; 0 = auto takes the register-moment kernel (phi_sort_weighted.hpp, asvgp_phi_last_algorithm = 16) where it applies - D = 1,
 // N >= 2, M <= 2048, 16-byte aligned x / y / w, a mesh that is an exact linspace - and the general kernel otherwise.
@@ -118,144 +119,4 @@ __global__ __launch_bounds__(64) void phi_wstats_accumulate_kernel(const double*
   }
 }
 
-// 256 partial images, 256 records of the weight sums, 256 column ranges (2 ints) of the register-moment kernel
-static size_t phi_weighted_ws_doubles(long M, int order) { return (size_t)PHI_MAX_BLOCKS * ((size_t)(order + 2) * (size_t)M + 1) + (size_t)PHI_MAX_BLOCKS * (PW_WCOLS + 1); }
-
-// Register-moment kernel.  Returns 1 when it does not apply (the conditions of launch_phi_sort, with w) and the caller takes the general kernel.
-template <int K>
-static int launch_phi_sort_weighted(Handle* h, const double* x, const double* y, const double* w, long N, long D, const double* mesh, long n_mesh,
-                                    double delta, long M, double* stats, double* wstats, double* ws, hipStream_t st) {
-  if (D != 1 || N < 2 || M > PS_NCELL ||
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w)) & 15) != 0) return 1;
-  double step = 0.0, m0 = 0.0, m_last = 0.0;
-  if (!handle_mesh_is_linspace(h, mesh, n_mesh, st, &step, &m0, &m_last)) return 1;
-  const double amax = fabs(m0) > fabs(m_last) ? fabs(m0) : fabs(m_last);
-  const double margin = 16.0 * 2.220446049250313e-16 * amax / delta + 1e-12;   // knot rounding over delta (as launch_phi_sort)
-  if (!(margin < 0.125)) return 1;
-  constexpr int TP = psw_tile_points<K>();
-  // (k = 4: 160 248 of 163 840 bytes.  A table that grows past the LDS must fail the build, not quietly hand the measured shape to kernel 11.)
-  static_assert(psw_lds_bytes<K, TP>() <= 160 * 1024 && ps_epilogue_bytes<K>() <= 160 * 1024, "weighted register-moment kernel: LDS plan exceeds 160 KB");
-  size_t lds_bytes = psw_lds_bytes<K, TP>();
-  if (ps_epilogue_bytes<K>() > lds_bytes) lds_bytes = ps_epilogue_bytes<K>();
-  const long nblk = (N + TP * PS_THREADS - 1) / (TP * PS_THREADS);   // at least one tile per workgroup
-  const long gmax = (h->phi_blocks > 0 && h->phi_blocks < PHI_MAX_BLOCKS) ? h->phi_blocks : PHI_MAX_BLOCKS;
-  const int G = (int)(nblk < 1 ? 1 : (nblk > gmax ? gmax : nblk));
-  long ppb = (N + G - 1) / G;
-  ppb = (ppb + 1) & ~1L;
-  if (ppb > 0x3fffffffL) return 1;                                   // (32-bit pair indices inside a workgroup)
-  PswArgs aw;
-  PsArgs& a = aw.p;
-  a.x = x; a.y = y; a.N = N; a.mesh_g = mesh; a.n_mesh = (int)n_mesh; a.inv_delta = 1.0 / delta; a.M = (int)M;
-  a.m0 = m0; a.m_last = m_last; a.step = step; a.smax_fast = 0.5 - margin;
-  a.partials = ws; a.ppb = ppb; a.zero_ptr = stats; a.zero_n = (K + 2) * M + 1; a.stamps = nullptr; a.stamps_wave = 0;
-  aw.w = w;
-  aw.wpart = ws + (size_t)PHI_MAX_BLOCKS * ((size_t)(K + 2) * (size_t)M + 1);
-  a.ranges = reinterpret_cast<int*>(aw.wpart + (size_t)PHI_MAX_BLOCKS * PW_WCOLS);   // (2 ints per workgroup: the fourth column's room and more - see phi_weighted_ws_doubles)
-  auto kern = phi_sort_weighted_kernel<K, TP>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) { set_error("hipFuncSetAttribute(%zu B LDS): %s", lds_bytes, hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-  const bool prof = h->prof_on && h->prof_n < PROF_RING && (h->prof_calls++ % h->prof_every == 0);
-  if (prof) (void)hipEventRecord(h->prof_ev[h->prof_n][0], st);
-  hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(PS_THREADS), lds_bytes, st, aw);
-  if (prof) { (void)hipEventRecord(h->prof_ev[h->prof_n][1], st); ++h->prof_n; }
-  const int E1 = (int)((K + 2) * M + 1);
-  const int gsplit = G >= 64 ? 16 : (G >= 8 ? 4 : 1);
-  hipLaunchKernelGGL(phi_reduce_kernel, dim3((E1 + 255) / 256, gsplit), dim3(256), 0, st, a.partials, G, (int)M, K, 0, M, 1L, 0, 1, stats, (const int*)a.ranges);
-  hipLaunchKernelGGL(phi_wstats_accumulate_kernel, dim3(1), dim3(64), 0, st, aw.wpart, G, wstats, 1);
-  return check_launch("phi_accumulate_1d_weighted (register moments)");
-}
-
-template <int K>
-static int launch_phi_weighted(Handle* h, const double* x, const double* y, const double* w, long N, long D, const double* mesh, long n_mesh,
-                               double delta, long M, double* stats, double* wstats, double* partials, hipStream_t st) {
-  { const int rcf = handle_flush_phi_reduce(h, nullptr, st); if (rcf) return rcf; }   // (a reduce parked on this workspace goes out first)
-  if (h->phi_algo == 3 || h->phi_algo == 5) {
-    set_error("phi_accumulate_1d_weighted: phi algorithm %d accumulates in fixed point, whose scales are bounds on the unweighted products - it has no weighted form (0 or 1)", h->phi_algo);
-    return ASVGP_ERR_UNSUPPORTED;
-  }
-  if (h->phi_algo == 0 || h->phi_algo == 6) {
-    const int rc = launch_phi_sort_weighted<K>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, partials, st);
-    if (rc != 1) { h->phi_last = 16; return rc; }
-    if (h->phi_algo == 6) { set_error("phi_accumulate_1d_weighted: phi algorithm 6 (register moments) needs D == 1, N >= 2, M <= 2048, 16-byte aligned x / y / w and a mesh that is an exact linspace"); return ASVGP_ERR_UNSUPPORTED; }
-  }
-  h->phi_last = 11;
-  const int ncells = (int)n_mesh - 1;
-  const int maxc = phi_max_cols(K, n_mesh, false);
-  if (maxc < 2 * K + 2) {
-    set_error("phi_accumulate_1d_weighted: mesh table (%ld knots) leaves no LDS for the band", n_mesh);
-    return ASVGP_ERR_LDS_CAPACITY;
-  }
-  const int cells_per_chunk = (M <= maxc) ? ncells : (maxc - K);
-  const long nblk = (N + PW_THREADS - 1) / PW_THREADS;
-  const long gmax = (h->phi_blocks > 0 && h->phi_blocks < PHI_MAX_BLOCKS) ? h->phi_blocks : PHI_MAX_BLOCKS;
-  const int G = (int)(nblk < 1 ? 1 : (nblk > gmax ? gmax : nblk));
-  long ppb = (N + G - 1) / G;
-  ppb = ((ppb + 63) / 64) * 64;
-  double* wpart = partials + (size_t)PHI_MAX_BLOCKS * ((size_t)(K + 2) * (size_t)M + 1);
-  const long zero_n = (K + 1) * M + M * D + 1;
-  bool zeroed = false;   // the first launched kernel zeroes the stats buffer
-  for (long dcol = 0; dcol < D; ++dcol) {
-    for (int cell0 = 0; cell0 < ncells; cell0 += cells_per_chunk) {
-      int cell1 = cell0 + cells_per_chunk;
-      if (cell1 > ncells) cell1 = ncells;
-      const int ncols = cell1 - cell0 + K;
-      const size_t lds_bytes = sizeof(double) * ((size_t)(K + 2) * ncols + n_mesh + 16);
-      const int do_band = (dcol == 0);
-      auto kern = phi_weighted_kernel<K>;
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute(%zu B LDS): %s", lds_bytes, hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-      const bool prof = h->prof_on && h->prof_n < PROF_RING && (h->prof_calls++ % h->prof_every == 0);
-      if (prof) (void)hipEventRecord(h->prof_ev[h->prof_n][0], st);
-      // (the weight sums: every chunk of the first output column writes its share of the rows; summed behind each of those launches)
-      hipLaunchKernelGGL(kern, dim3(G), dim3(PW_THREADS), lds_bytes, st, x, y + dcol, (long)D, w, N, mesh, (int)n_mesh, 1.0 / delta, cell0, cell1,
-                         ncols, do_band, partials, wpart, ppb, zeroed ? (double*)nullptr : stats, zero_n);
-      if (prof) { (void)hipEventRecord(h->prof_ev[h->prof_n][1], st); ++h->prof_n; }
-      const int E1 = (K + 2) * ncols + 1;
-      const int gsplit = G >= 64 ? 16 : (G >= 8 ? 4 : 1);
-      hipLaunchKernelGGL(phi_reduce_kernel, dim3((E1 + 255) / 256, gsplit), dim3(256), 0, st, partials, G, ncols, K, cell0, M, D, (int)dcol, do_band, stats,
-                         (const int*)nullptr);
-      if (do_band) hipLaunchKernelGGL(phi_wstats_accumulate_kernel, dim3(1), dim3(64), 0, st, wpart, G, wstats, zeroed ? 0 : 1);
-      zeroed = true;
-    }
-  }
-  return check_launch("phi_accumulate_1d_weighted");
-}
-
 }  // namespace asvgp
-
-using namespace asvgp;
-
-extern "C" size_t asvgp_phi_weighted_workspace_bytes(int64_t M, int order, int64_t D) {
-  (void)D;
-  if (M <= 0 || order < 1 || order > ASVGP_MAX_ORDER) return 0;
-  const size_t own = sizeof(double) * phi_weighted_ws_doubles((long)M, order);
-  const size_t base = asvgp_phi_workspace_bytes(M, order, D);   // (never less: a model keeps ONE workspace for both entries)
-  return own > base ? own : base;
-}
-
-extern "C" int asvgp_phi_accumulate_1d_weighted(asvgp_handle_t handle, const double* x, const double* y, const double* w, int64_t N, int64_t D,
-                                                const double* mesh, int64_t n_mesh, double delta, int order, int64_t M, double* stats,
-                                                double* wstats, void* workspace, size_t workspace_bytes, asvgp_stream_t stream) {
-  if (((!x || !y || !w) && N > 0) || !mesh || !stats || !wstats || N < 0 || D < 1 || M < 1 || !(delta > 0.0)) {
-    set_error("phi_accumulate_1d_weighted: bad argument");
-    return ASVGP_ERR_BAD_ARG;
-  }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("phi_accumulate_1d_weighted: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  if (n_mesh != M - order + 1 || n_mesh < 2) { set_error("phi_accumulate_1d_weighted: n_mesh=%ld != M-order+1", (long)n_mesh); return ASVGP_ERR_BAD_ARG; }
-  if (M > 0x3fffffff) { set_error("phi_accumulate_1d_weighted: M too large"); return ASVGP_ERR_UNSUPPORTED; }
-  if (!workspace || workspace_bytes < asvgp_phi_weighted_workspace_bytes(M, order, D)) {
-    set_error("phi_accumulate_1d_weighted: workspace too small (%zu < %zu)", workspace_bytes, asvgp_phi_weighted_workspace_bytes(M, order, D));
-    return ASVGP_ERR_WORKSPACE;
-  }
-  hipStream_t st = as_stream(stream);
-  Handle* h = as_handle(handle);
-  double* part = static_cast<double*>(workspace);
-  switch (order) {
-    case 1: return launch_phi_weighted<1>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, part, st);
-    case 2: return launch_phi_weighted<2>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, part, st);
-    case 3: return launch_phi_weighted<3>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, part, st);
-    case 4: return launch_phi_weighted<4>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, part, st);
-    case 5: return launch_phi_weighted<5>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, part, st);
-    default: return launch_phi_weighted<6>(h, x, y, w, N, D, mesh, n_mesh, delta, M, stats, wstats, part, st);
-  }
-}

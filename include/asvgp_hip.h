@@ -155,6 +155,21 @@ int asvgp_set_phi_workgroups(asvgp_handle_t handle, int n);
  * caller thereby keeps its N-side stream to the streaming kernels alone.  asvgp_phi_reduce_1d without a pending reduce is a no-op. */
 int asvgp_set_phi_deferred_reduce(asvgp_handle_t handle, int on);
 int asvgp_phi_reduce_1d(asvgp_handle_t handle, asvgp_stream_t stream);
+/* Host-only: the launch plan of asvgp_phi_accumulate_1d (weighted = 0) or asvgp_phi_accumulate_1d_weighted (1) for these inputs, as the
+ * entries themselves compute it before they launch anything - no handle, no device.  Inputs: the handle's asvgp_set_phi_algorithm,
+ * asvgp_set_phi_workgroups and asvgp_set_phi_deferred_reduce; the entry's N, D, M, order, n_mesh, delta; whether x, y (and w) are 16-byte
+ * aligned; and the two facts an entry finds out on the device, only once a rule depends on them: whether the mesh is an exact
+ * numpy.linspace, with its first and last knot, and whether x is a time series (asvgp_set_phi_input_order).
+ * plan16_host: [0] status, [1] kernel (what asvgp_phi_last_algorithm reports), [2] 1 = the tile sort's time-series instantiation
+ * (asvgp_phi_last_input_order = 2), [3] points per thread and tile (6, 16) or the moment image's plane stride (5), [4] dynamic LDS bytes
+ * (band scatter: of the widest chunk), [5] workgroups, [6] points per workgroup, [7] column chunks per output column, [8] mesh cells per
+ * chunk, [9] kernel launches, [10] reduce launches made by the call (0: left to asvgp_phi_reduce_1d), [11] grid.y of the reduce,
+ * [12] the fixed-point exponent s0 (-1: no fixed point), [13] / [14] 1 = the plan had to know whether the mesh is regular / the input
+ * order, [15] 0.  Returns the status: ASVGP_OK, or what the launch would be refused with (asvgp_last_error_string says why).  For the
+ * CPU tests. */
+int asvgp_phi_launch_plan_host(int phi_algorithm, int phi_workgroups, int deferred_reduce, int weighted, int64_t N, int64_t D, int64_t M, int order,
+                               int64_t n_mesh, double delta, int aligned16, int mesh_regular, double mesh_first, double mesh_last, int series,
+                               int64_t* plan16_host);
 
 /* ------------------------------------------------------------------------------------------------
  * Per-observation noise weights.  Observation i carries noise variance sigma2 / w_i (w_i >= 0 fixed and finite, sigma2 still the

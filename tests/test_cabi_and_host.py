@@ -506,6 +506,119 @@ def test_fused_elbo_launch_plan_follows_the_documented_rules(lib):
     assert lib.asvgp_elbo_launch_plan_host(0, 0, 0, 0, 64, 7, 1, 0, 1, 1, 0, 0, 0, 0, 0, 0, out.ctypes.data) == UNSUPPORTED
 
 
+PHI_FIELDS = ("status", "kernel", "series", "shape", "lds", "G", "ppb", "chunks", "cells", "launches", "reduces", "reduce_y", "s0", "asked_mesh",
+              "asked_order", "zero")                                              # plan16 of asvgp_phi_launch_plan_host
+LDS_MAX = 160 * 1024
+
+
+def _phi_plan(lib, N=10 ** 7, M=2048, k=4, D=1, algo=0, wg=0, defer=0, weighted=0, aligned=1, regular=1, first=0.0, last=1.0, series=0, delta=None,
+              n_mesh=None):
+    """(status, fields by name) of asvgp_phi_launch_plan_host for the uniform mesh of (M, k) on [first, last]"""
+    n_mesh = M - k + 1 if n_mesh is None else n_mesh
+    delta = (last - first) / (n_mesh - 1) if delta is None else delta
+    out = np.full(16, -99, dtype=np.int64)
+    rc = lib.asvgp_phi_launch_plan_host(algo, wg, defer, weighted, N, D, M, k, n_mesh, delta, aligned, regular, first, last, series, out.ctypes.data)
+    p = dict(zip(PHI_FIELDS, (int(v) for v in out)))
+    assert p["status"] == rc and p["zero"] == 0
+    return rc, p
+
+
+def test_phi_launch_plan_follows_the_documented_rules(lib):
+    """asvgp_phi_launch_plan_host is the plan_phi that asvgp_phi_accumulate_1d and asvgp_phi_accumulate_1d_weighted call before they launch
+    anything (csrc/phi_launch.hpp).  Which kernel and shape a given input gets, written down from the rules (include/asvgp_hip.h:
+    asvgp_set_phi_algorithm, asvgp_phi_accumulate_1d_weighted) and the constants of the sources: 1024 threads, 6 / 4 points per thread and
+    tile at k = 4 (plain / time series), 2048-cell images, plane strides 512 / 1024 / 2048, at most 256 workgroups, reduce slices 16 / 4 / 1
+    from 64 / 8 workgroups on.  The cases sit away from the LDS thresholds, so no expectation is a byte count."""
+    def plan(**kw):
+        rc, p = _phi_plan(lib, **kw)
+        assert rc == OK, lib.asvgp_last_error_string()
+        assert 0 < p["lds"] <= LDS_MAX and p["G"] >= 1 and p["launches"] >= 1
+        return p
+
+    def refused(**kw):
+        return _phi_plan(lib, **kw)[0]
+
+    def s0_of(ppb):                                                # 62 - ceil(log2(points per workgroup)), at most 50
+        return min(50, 62 - int(np.ceil(np.log2(ppb))))
+
+    # the headline shape: the tile sort, plain instantiation, one launch and one reduce over 16 slices of the 256 partials
+    p = plan()
+    assert (p["kernel"], p["series"], p["shape"], p["G"]) == (6, 0, 6, 256) and p["ppb"] % 2 == 0 and p["ppb"] * 256 >= 10 ** 7
+    assert (p["launches"], p["reduces"], p["reduce_y"], p["chunks"], p["cells"], p["s0"]) == (1, 1, 16, 1, 2044, -1)
+    assert (p["asked_mesh"], p["asked_order"]) == (1, 1)
+    p = plan(series=1)
+    assert (p["kernel"], p["series"], p["shape"], p["G"]) == (6, 1, 4, 256) and p["ppb"] % 128 == 0
+    assert plan(wg=240)["G"] == 240
+    p = plan(defer=1)
+    assert (p["kernel"], p["launches"], p["reduces"]) == (6, 1, 0)
+    assert plan(algo=6)["kernel"] == 6
+    # the tile sort does not apply: the centred moments, and the input order is never consulted
+    for kw in (dict(N=1), dict(regular=0), dict(first=1e15, last=1e15 + 2.044, delta=1e-3)):   # one point | irregular mesh | no margin for the cell guess
+        p = plan(**kw)
+        assert (p["kernel"], p["shape"], p["asked_mesh"], p["asked_order"]) == (5, 2048, 1, 0), kw
+        assert (p["launches"], p["reduces"], p["chunks"]) == (1, 1, 1) and p["ppb"] % 2048 == 0 and p["s0"] == s0_of(p["ppb"]), kw
+    assert plan(N=1)["G"] == 1 and plan(regular=0)["G"] == 256
+    assert plan(regular=0, defer=1)["reduces"] == 0
+    assert plan(M=64, regular=0)["shape"] == 512 and plan(M=1000, regular=0)["shape"] == 1024   # the smallest stride that holds the cells
+    assert plan(algo=5)["kernel"] == 5
+    # M = 2049: the first the tile sort's 2048-cell image does not hold; its 2045 cells still lie under the moments' largest stride.
+    # M = 3000: neither image holds it - the fixed-point band scatter, in column chunks
+    p = plan(M=2049)
+    assert (p["kernel"], p["shape"], p["asked_order"]) == (5, 2048, 0)
+    p = plan(M=3000)
+    assert (p["kernel"], p["series"], p["shape"]) == (3, 0, 0) and p["chunks"] > 1 and p["chunks"] * p["cells"] >= 3000 - 4
+    assert (p["chunks"] - 1) * p["cells"] < 3000 - 4 and p["launches"] == p["chunks"] and p["reduces"] == p["launches"]
+    assert p["ppb"] % 2048 == 0 and p["s0"] == s0_of(p["ppb"])
+    # more than one output column, or inputs off the 16-byte boundary: the band scatter, and the mesh is never consulted
+    for kw in (dict(D=2), dict(aligned=0)):
+        p = plan(**kw)
+        assert (p["kernel"], p["asked_mesh"], p["asked_order"], p["chunks"], p["cells"]) == (3, 0, 0, 1, 2044), kw
+        assert p["launches"] == kw.get("D", 1) and p["reduces"] == p["launches"] and p["s0"] == s0_of(p["ppb"]), kw
+    p = plan(M=3000, D=2)
+    assert p["kernel"] == 3 and p["launches"] == 2 * p["chunks"]
+    assert plan(D=2, defer=1)["reduces"] == 2                     # (only the single-launch kernels park their reduce)
+    # forced algorithms
+    p = plan(algo=1)
+    assert (p["kernel"], p["s0"], p["asked_mesh"], p["asked_order"]) == (1, -1, 0, 0)
+    p = plan(algo=3)
+    assert (p["kernel"], p["asked_mesh"]) == (3, 0) and p["s0"] == s0_of(p["ppb"])
+    for kw in (dict(D=2), dict(M=2049)):
+        assert refused(algo=6, **kw) == UNSUPPORTED, kw
+        assert b"tile sort" in lib.asvgp_last_error_string()
+    assert refused(algo=5, D=2) == UNSUPPORTED
+    assert b"algorithm 5" in lib.asvgp_last_error_string()
+    # weighted: the register moments where the tile sort would apply, else the weighted band scatter; never fixed point, never deferred
+    p = plan(weighted=1)
+    assert (p["kernel"], p["series"], p["shape"], p["G"], p["s0"], p["asked_mesh"], p["asked_order"]) == (16, 0, 4, 256, -1, 1, 0)
+    assert (p["launches"], p["reduces"], p["reduce_y"]) == (1, 1, 16) and p["ppb"] % 2 == 0
+    assert plan(weighted=1, series=1)["series"] == 0 and plan(weighted=1, algo=6)["kernel"] == 16
+    for kw in (dict(D=2), dict(algo=1), dict(regular=0), dict(M=2049), dict(aligned=0), dict(N=1)):
+        p = plan(weighted=1, **kw)
+        assert (p["kernel"], p["s0"], p["chunks"]) == (11, -1, 1) and p["ppb"] % 64 == 0, kw
+    assert plan(weighted=1, D=2)["asked_mesh"] == 0 and plan(weighted=1, algo=1)["asked_mesh"] == 0
+    p = plan(weighted=1, M=3000)                                   # (without the fixed-point plane the LDS holds about 2900 columns at k = 4)
+    assert p["kernel"] == 11 and p["chunks"] > 1 and p["chunks"] * p["cells"] >= 3000 - 4 and p["launches"] == p["chunks"]
+    for algo in (3, 5):
+        assert refused(weighted=1, algo=algo) == UNSUPPORTED
+        err = lib.asvgp_last_error_string()
+        assert b"fixed point" in err and b"algorithm %d" % algo in err and b"phi_accumulate_1d_weighted" in err
+    assert refused(weighted=1, algo=6, D=3) == UNSUPPORTED
+    assert b"register moments" in lib.asvgp_last_error_string()
+    assert plan(weighted=1, defer=1)["reduces"] == 1 and plan(weighted=1, D=2, defer=1)["reduces"] == 2
+    # small grids: at least one tile (6 x 1024 points) per workgroup; the reduce takes 16 / 4 / 1 slices from 64 / 8 workgroups on
+    p = plan(N=5000)
+    assert (p["kernel"], p["G"], p["reduce_y"]) == (6, 1, 1) and p["ppb"] >= 5000
+    p = plan(N=20 * 6144)
+    assert (p["kernel"], p["G"], p["reduce_y"]) == (6, 20, 4)
+    assert [plan(wg=g)["reduce_y"] for g in (7, 8, 63, 64)] == [1, 4, 4, 16]
+    assert plan(N=0)["kernel"] == 3 and plan(N=0)["G"] == 1       # nothing to stream: the band scatter zeroes the statistics
+    # argument checks of the entry itself
+    assert lib.asvgp_phi_launch_plan_host(0, 0, 0, 0, 1000, 1, 64, 4, 61, 0.1, 1, 1, 0.0, 6.0, 0, None) == BAD_ARG
+    assert refused(M=64, k=7, n_mesh=58) == UNSUPPORTED and b"order 7" in lib.asvgp_last_error_string()
+    assert refused(M=64, n_mesh=60) == BAD_ARG and b"n_mesh" in lib.asvgp_last_error_string()
+    assert refused(algo=2) == BAD_ARG and refused(wg=257) == BAD_ARG and refused(D=0) == BAD_ARG
+
+
 def test_two_sided_factorisation_layout_invariants():
     """asvgp_amd.kronecker.twisted_layout (host logic of GPR_kron's two-sided band Cholesky): for every size both systems have nb super-blocks,
     the separator is their last block, paddings are non-negative, the interiors do not overlap and together with the separator cover

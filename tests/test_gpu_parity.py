@@ -223,6 +223,90 @@ def test_phi_large_M_column_chunks(A):
     assert abs(m.tr_yTy.item() - yy) <= 1e-12 * yy
 
 
+def _weighted_stats_1d():
+    """the direct fp64 accumulation of the weighted statistics that tests/test_weighted_obs.py checks the weighted entry against"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_weighted_obs_yardsticks", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_weighted_obs.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.weighted_stats_1d
+
+
+# (order, M, N, D, weighted, phi algorithm, input order, workgroups, mesh range, x off the 16-byte boundary) -> the kernel the rules name
+PHI_PLAN_CASES = [
+    ((4, 64, 20000, 1, 0, 0, 1, 0, (0, 1), False), 6),              # the tile sort, told the input is unsorted
+    ((4, 64, 20000, 1, 0, 0, 2, 0, (0, 1), False), 6),              # ... told it is a time series
+    ((4, 64, 1, 1, 0, 0, 0, 0, (0, 1), False), 5),                  # one point: the tile sort needs a pair
+    ((3, 100, 20000, 1, 0, 0, 0, 0, (-3.5, 10.5), False), 5),       # float32-linspace mesh: not an exact linspace
+    ((4, 3000, 20000, 1, 0, 0, 0, 0, (0, 1), False), 3),            # neither image holds 3000 columns: chunked band scatter
+    ((4, 64, 20000, 2, 0, 0, 0, 0, (0, 1), False), 3),              # two output columns
+    ((4, 64, 20000, 1, 0, 1, 0, 0, (0, 1), False), 1),              # forced
+    ((4, 64, 20000, 1, 0, 0, 0, 0, (0, 1), True), 3),               # x = buf[1:]
+    ((4, 64, 20000, 1, 1, 0, 0, 0, (0, 1), False), 16),             # weighted: register moments
+    ((4, 64, 20000, 2, 1, 0, 0, 0, (0, 1), False), 11),             # weighted, two output columns
+    ((4, 3000, 20000, 1, 1, 0, 0, 0, (0, 1), False), 11),           # weighted, chunked
+    ((4, 64, 20000, 1, 0, 0, 0, 3, (0, 1), False), 6),              # three workgroups
+]
+
+
+@pytest.mark.parametrize("case,kernel", PHI_PLAN_CASES)
+def test_phi_launch_plan_names_the_kernel_that_runs(A, case, kernel):
+    """The real entries (asvgp_phi_accumulate_1d, asvgp_phi_accumulate_1d_weighted through the library, own handle) on the smallest inputs
+    that take each branch of the launch plan: asvgp_phi_last_algorithm and asvgp_phi_last_input_order are fields [1] and [2] of
+    asvgp_phi_launch_plan_host for the same inputs, and the statistics are the direct fp64 accumulation's to 1e-12 of the largest entry
+    (include/asvgp_hip.h, asvgp_set_phi_algorithm)."""
+    from asvgp_amd import _lib
+    lib = _lib.get_lib()
+    k, M, N, D, weighted, algo, order, wg, (a, b), misaligned = case
+    rng = np.random.default_rng(1000 * k + M + N + 7 * D + weighted)
+    ob = O.Basis(k, a, b, M)
+    mesh = np.asarray(ob.mesh, dtype=np.float64)
+    n_mesh = mesh.shape[0]
+    x = rng.uniform(a + 1e-9 * (b - a), b - 1e-9 * (b - a), N)
+    y = np.sin(20 * x)[:, None] + 0.1 * rng.normal(size=(N, D))
+    w = rng.integers(0, 4, N).astype(np.float64) if weighted else None
+    if weighted:
+        band, rhs, yy, (sw, lam, npos) = _weighted_stats_1d()(ob, x, y, w)
+    else:
+        band, rhs, yy = O.sufficient_stats_direct(ob, x, y)
+    x_t = dev(np.concatenate([[0.0], x]))[1:] if misaligned else dev(x)
+    y_t, mesh_t = dev(y), dev(mesh)
+    assert (x_t.data_ptr() % 16 == 8) == misaligned and y_t.data_ptr() % 16 == 0
+    # the plan for these inputs: the mesh fact as the library decides it (knot i = i * step + first, two roundings), the order as told
+    step = (mesh[-1] - mesh[0]) / (n_mesh - 1)
+    regular = int(np.array_equal(mesh[:-1], np.arange(n_mesh - 1) * step + mesh[0]))
+    assert regular == (0 if a == -3.5 else 1)
+    plan = np.full(16, -99, dtype=np.int64)
+    assert lib.asvgp_phi_launch_plan_host(algo, wg, 0, weighted, N, D, M, k, n_mesh, float(ob.delta), int(not misaligned), regular, float(mesh[0]),
+                                          float(mesh[-1]), int(order == 2), plan.ctypes.data) == 0, lib.asvgp_last_error_string()
+    assert plan[1] == kernel
+    h = _lib.Handle()
+    h.set_phi_algorithm(algo)
+    h.set_phi_input_order(order)
+    h.set_phi_workgroups(wg)
+    stats = torch.full(((k + 1) * M + M * D + 1,), 7.0, dtype=torch.float64, device="cuda")     # (the entry overwrites it)
+    wsb = (lib.asvgp_phi_weighted_workspace_bytes if weighted else lib.asvgp_phi_workspace_bytes)(M, k, D)
+    ws = torch.empty(wsb // 8, dtype=torch.float64, device="cuda")
+    if weighted:
+        w_t = dev(w)
+        wst = torch.full((3,), 7.0, dtype=torch.float64, device="cuda")
+        rc = lib.asvgp_phi_accumulate_1d_weighted(h.ptr, x_t.data_ptr(), y_t.data_ptr(), w_t.data_ptr(), N, D, mesh_t.data_ptr(), n_mesh, float(ob.delta), k, M,
+                                                  stats.data_ptr(), wst.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr())
+    else:
+        rc = lib.asvgp_phi_accumulate_1d(h.ptr, x_t.data_ptr(), y_t.data_ptr(), N, D, mesh_t.data_ptr(), n_mesh, float(ob.delta), k, M, stats.data_ptr(),
+                                         ws.data_ptr(), wsb, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0, lib.asvgp_last_error_string()
+    assert h.phi_last_algorithm() == plan[1] and h.phi_last_input_order() == 1 + plan[2]
+    st = stats.cpu().numpy()
+    got_band, got_rhs, got_yy = st[:(k + 1) * M].reshape(k + 1, M), st[(k + 1) * M:-1].reshape(M, D), float(st[-1])
+    assert np.max(np.abs(got_band - band)) <= 1e-12 * np.max(np.abs(band))
+    assert np.max(np.abs(got_rhs - rhs)) <= 1e-12 * np.max(np.abs(rhs))
+    assert abs(got_yy - yy) <= 1e-12 * yy
+    if weighted:
+        assert abs(wst[0].item() - sw) <= 1e-12 * sw and wst[2].item() == npos
+
+
 # ------------------------------------------------------------------------------------------------ banded ops
 def _spd_band(rng, k, M):
     Bm = rng.normal(size=(M, M))
