@@ -331,48 +331,6 @@ static int dispatch_k(int k, Args... args) {
     default: set_error("bandwidth %d outside 1..%d", k, (int)ASVGP_MAX_BANDWIDTH); return ASVGP_ERR_UNSUPPORTED;
   }
 }
-template <int K> struct CholLauncher {
-  static int run(const double* A, double* L, int M, int* info, hipStream_t st) {
-    constexpr int W = K + 1;
-    static const bool lds_off = getenv("ASVGP_BAND_OPS_LDS") && atoi(getenv("ASVGP_BAND_OPS_LDS")) == 0;      // (0: the register-window sweep always)
-    static const int seg_env = getenv("ASVGP_BAND_OPS_SEG_BLOCKS") ? atoi(getenv("ASVGP_BAND_OPS_SEG_BLOCKS")) : 0;     // (tests: short segments)
-    if (!lds_off && M > K + 1 && M < (1 << 30)) {
-      int cap = (156 * 1024) / (8 * W);               // columns the LDS holds
-      int seg = M <= cap ? (M + W - 1) / W : (cap - W) / W;     // one segment when the band fits, else cap - (k+1) columns per segment
-      if (seg_env >= 1 && seg_env < seg) { seg = seg_env; cap = seg * W + W; }
-      else if (M <= cap) cap = M;
-      const size_t lds_bytes = sizeof(double) * (size_t)W * (size_t)cap;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(cholesky_band_lds_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess) {
-        hipLaunchKernelGGL(cholesky_band_lds_kernel<K>, dim3(1), dim3(256), lds_bytes, st, A, L, M, info, seg);
-        return check_launch("cholesky_band (band in the LDS)");
-      }
-      (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(cholesky_band_kernel<K>, dim3(1), dim3(64), 0, st, A, L, M, info);
-    return check_launch("cholesky_band");
-  }
-};
-template <int K> struct TakaLauncher {
-  static int run(const double* L, double* S, int M, hipStream_t st) {
-    constexpr int W = K + 1;
-    static const bool lds_off = getenv("ASVGP_BAND_OPS_LDS") && atoi(getenv("ASVGP_BAND_OPS_LDS")) == 0;
-    static const int seg_env = getenv("ASVGP_BAND_OPS_SEG_BLOCKS") ? atoi(getenv("ASVGP_BAND_OPS_SEG_BLOCKS")) : 0;     // (tests: short segments)
-    if (!lds_off && M > 2 * K + 1 && M < (1 << 30)) {
-      int cap = (156 * 1024) / (8 * W);               // columns the LDS holds
-      int seg = M <= cap ? (M + K - 1) / K : (cap - 1) / K;     // blocks of k columns: one segment when the band fits, else cap - 1 columns per segment
-      if (seg_env >= 1 && seg_env < seg) { seg = seg_env; cap = seg * K + 1; }
-      else if (M <= cap) cap = M;
-      const size_t lds_bytes = sizeof(double) * (size_t)W * (size_t)cap;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(takahashi_lds_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess) {
-        hipLaunchKernelGGL(takahashi_lds_kernel<K>, dim3(1), dim3(256), lds_bytes, st, L, S, M, seg);
-        return check_launch("inverse_from_cholesky_band (band in the LDS)");
-      }
-      (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(takahashi_kernel<K>, dim3(1), dim3(64), 0, st, L, S, M);
-    return check_launch("inverse_from_cholesky_band");
-  }
-};
 template <int K> struct TrsvLauncher {
   static int run(const double* L, int M, const double* B, double* X, long D, int trans, hipStream_t st) {
     hipLaunchKernelGGL(trsv_kernel<K>, dim3((unsigned)D), dim3(64), 0, st, L, M, B, X, D, trans);
@@ -459,18 +417,6 @@ static int band_args_ok(const void* a, const void* b, int64_t M, int k, const ch
   if (M > 0x3fffffff) { set_error("%s: M too large", who); return ASVGP_ERR_UNSUPPORTED; }
   if (k < 1 || k > ASVGP_MAX_BANDWIDTH) { set_error("%s: bandwidth %d outside 1..%d", who, k, (int)ASVGP_MAX_BANDWIDTH); return ASVGP_ERR_UNSUPPORTED; }
   return ASVGP_OK;
-}
-
-extern "C" int asvgp_cholesky_band(const double* K, double* L, int64_t M, int k, int* info, asvgp_stream_t stream) {
-  int rc = band_args_ok(K, L, M, k, "cholesky_band");
-  if (rc) return rc;
-  return dispatch_k<CholLauncher>(k, K, L, (int)M, info, as_stream(stream));
-}
-
-extern "C" int asvgp_inverse_from_cholesky_band(const double* L, double* S, int64_t M, int k, asvgp_stream_t stream) {
-  int rc = band_args_ok(L, S, M, k, "inverse_from_cholesky_band");
-  if (rc) return rc;
-  return dispatch_k<TakaLauncher>(k, L, S, (int)M, as_stream(stream));
 }
 
 extern "C" int asvgp_solve_triang_mat(const double* L, const double* B, double* X, int64_t M, int k, int64_t D,
@@ -817,7 +763,7 @@ __global__ __launch_bounds__(256) void band_takahashi_vjp_lds_kernel(const doubl
   constexpr int W = K + 1;
   double* Bs = sh;                                    // incoming adjoint of S by ROWS: (r, r - d) at [(r - rbase) W + d] (a row enters the window at a time)
   double* Fq = sh + (long)cap_rows * W;               // accb(j + a, j) at [(j - c0) W + a], then the column's results
-  int* prog = reinterpret_cast<int*>(Fq + cap_fq - 1);   // columns wave 0 has finished (a slot no column uses: see the launcher)
+  int* prog = reinterpret_cast<int*>(Fq + cap_fq - 1);   // columns wave 0 has finished (a slot no column uses: see plan_band_op)
   const int tid = threadIdx.x;
   const int nblk = (M + W - 1) / W;
   int c0 = 0, c1 = 0, rbase = 0;
@@ -1035,75 +981,6 @@ __global__ __launch_bounds__(256) void band_takahashi_vjp_lds_kernel(const doubl
   }
 }
 
-template <int K> struct TakaVjpLdsLauncher {
-  static int run(const double* L, const double* S, const double* Sbar, double* Lbar, double* work, int M, hipStream_t st) {
-    if constexpr (K <= 6) {                           // (k = 7, 8: the windows and the blocks fetched ahead no longer fit the register file)
-      constexpr int W = K + 1;
-      const int nblk = (M + W - 1) / W;
-      // one segment: rows and factor columns of the whole matrix, the counter in the slot of (row M - 1 + k, column M - 1), which no column
-      // uses; several: seg W + W rows, seg W columns and one more double for the counter
-      int seg, cap_rows, cap_fq;
-      static const int seg_env = getenv("ASVGP_BAND_OPS_SEG_BLOCKS") ? atoi(getenv("ASVGP_BAND_OPS_SEG_BLOCKS")) : 0;   // (tests: short segments)
-      if ((size_t)2 * M * W * sizeof(double) <= 160 * 1024 && !(seg_env >= 2 && seg_env < nblk)) { seg = nblk; cap_rows = M; cap_fq = M * W; }
-      else {
-        const int doubles = 160 * 1024 / (int)sizeof(double);
-        seg = ((doubles - 1) / W - W) / (2 * W);
-        if (seg_env >= 2 && seg_env < seg) seg = seg_env;
-        cap_rows = seg * W + W;
-        cap_fq = seg * W * W + 1;
-      }
-      if (seg < 2) return 1;
-      const size_t bytes = sizeof(double) * ((size_t)cap_rows * W + (size_t)cap_fq);
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_takahashi_vjp_lds_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (e != hipSuccess) { (void)hipGetLastError(); return 1; }
-      hipLaunchKernelGGL(band_takahashi_vjp_lds_kernel<K>, dim3(1), dim3(256), bytes, st, L, S, Sbar, Lbar, work, M, seg, cap_rows, cap_fq);
-      return check_launch("inverse_from_cholesky_band_vjp (register window)");
-    } else {
-      return 1;
-    }
-  }
-};
-template <int K> struct CholVjpLdsLauncher {
-  static int run(const double* L, const double* Lbar, double* Kbar, int M, hipStream_t st) {
-    constexpr int W = K + 1;
-    int cap = (160 * 1024) / (16 * W);                // columns of both arrays the LDS holds
-    int seg = M <= cap ? (M + W - 1) / W : (cap - W) / W;       // one segment when everything fits, else cap - (k+1) columns per segment
-    static const int seg_env = getenv("ASVGP_BAND_OPS_SEG_BLOCKS") ? atoi(getenv("ASVGP_BAND_OPS_SEG_BLOCKS")) : 0;     // (tests: short segments)
-    if (seg_env >= 2 && seg_env < seg) { seg = seg_env; cap = seg * W + W; }
-    else if (M <= cap) cap = M;
-    if (seg < 2) return 1;
-    const size_t bytes = sizeof(double) * 2 * (size_t)cap * W;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_cholesky_vjp_lds_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return 1; }
-    hipLaunchKernelGGL(band_cholesky_vjp_lds_kernel<K>, dim3(1), dim3(256), bytes, st, L, Lbar, Kbar, M, seg, cap);
-    return check_launch("cholesky_band_vjp (register window)");
-  }
-};
-template <int K> struct CholVjpWaveLauncher {
-  static int run(const double* L, const double* Lbar, double* Kbar, int M, size_t bytes, hipStream_t st) {
-    if constexpr ((K + 1) * (K + 1) <= 64) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_cholesky_vjp_wave_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-      hipLaunchKernelGGL(band_cholesky_vjp_wave_kernel<K>, dim3(1), dim3(256), bytes, st, L, Lbar, Kbar, M);
-      return check_launch("cholesky_band_vjp");
-    } else {
-      return 1;
-    }
-  }
-};
-template <int K> struct TakaVjpWaveLauncher {
-  static int run(const double* L, const double* S, const double* Sbar, double* Lbar, double* work, int M, size_t bytes, hipStream_t st) {
-    if constexpr ((K + 1) * (K + 1) <= 64) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_takahashi_vjp_wave_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-      hipLaunchKernelGGL(band_takahashi_vjp_wave_kernel<K>, dim3(1), dim3(256), bytes, st, L, S, Sbar, Lbar, work, M);
-      return check_launch("inverse_from_cholesky_band_vjp");
-    } else {
-      return 1;
-    }
-  }
-};
-
 // out[d, j] = sign * sum_c U[j + d, c] V[j, c]   (d = 0..k): the lower band of sign * U V^T  (Lbar of the triangular solves)
 __global__ void band_outer_kernel(const double* __restrict__ U, const double* __restrict__ V, long M, long D, int k, double sign, double* __restrict__ out) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1115,52 +992,8 @@ __global__ void band_outer_kernel(const double* __restrict__ U, const double* __
   out[e] = sign * acc;
 }
 
-extern "C" int asvgp_cholesky_band_vjp(const double* L, const double* Lbar, double* Kbar, double* work, int64_t M, int k, asvgp_stream_t stream) {
-  int rc = band_args_ok(L, Lbar, M, k, "cholesky_band_vjp");
-  if (rc) return rc;
-  if (!Kbar || !work) { set_error("cholesky_band_vjp: bad argument"); return ASVGP_ERR_BAD_ARG; }
-  const size_t bytes = sizeof(double) * 2 * (size_t)(k + 1) * (size_t)M;
-  const int use_lds = bytes <= 160 * 1024;
-  static const bool lds_off = getenv("ASVGP_BAND_OPS_LDS") && atoi(getenv("ASVGP_BAND_OPS_LDS")) == 0;
-  if (!lds_off && M > 2 * (k + 1) && M < (1 << 30)) {           // lane-uniform register window (round 4), any M (segments)
-    const int rcl = dispatch_k<CholVjpLdsLauncher>(k, L, Lbar, Kbar, (int)M, as_stream(stream));
-    if (rcl != 1) return rcl;
-  }
-  if (use_lds && (k + 1) * (k + 1) <= 64) {                     // wave-parallel form
-    const int rcw = dispatch_k<CholVjpWaveLauncher>(k, L, Lbar, Kbar, (int)M, bytes, as_stream(stream));
-    if (rcw != 1) return rcw;
-  }
-  if (use_lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_cholesky_vjp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-  }
-  hipLaunchKernelGGL(band_cholesky_vjp_kernel, dim3(1), dim3(256), use_lds ? bytes : 0, as_stream(stream), L, Lbar, Kbar, work, (int)M, k, use_lds);
-  return check_launch("cholesky_band_vjp");
-}
-
-extern "C" int asvgp_inverse_from_cholesky_band_vjp(const double* L, const double* S, const double* Sbar, double* Lbar, double* work, int64_t M,
-                                                    int k, asvgp_stream_t stream) {
-  int rc = band_args_ok(L, S, M, k, "inverse_from_cholesky_band_vjp");
-  if (rc) return rc;
-  if (!Sbar || !Lbar || !work) { set_error("inverse_from_cholesky_band_vjp: bad argument"); return ASVGP_ERR_BAD_ARG; }
-  const size_t bytes = sizeof(double) * 2 * (size_t)(k + 1) * (size_t)M;
-  const int use_lds = bytes <= 160 * 1024;
-  static const bool lds_off = getenv("ASVGP_BAND_OPS_LDS") && atoi(getenv("ASVGP_BAND_OPS_LDS")) == 0;
-  if (!lds_off && M > 2 * (k + 1) && M < (1 << 30)) {           // lane-uniform register windows on two waves (round 4), any M (segments)
-    const int rcl = dispatch_k<TakaVjpLdsLauncher>(k, L, S, Sbar, Lbar, work, (int)M, as_stream(stream));
-    if (rcl != 1) return rcl;
-  }
-  if (use_lds && (k + 1) * (k + 1) <= 64) {                     // wave-parallel form
-    const int rcw = dispatch_k<TakaVjpWaveLauncher>(k, L, S, Sbar, Lbar, work, (int)M, bytes, as_stream(stream));
-    if (rcw != 1) return rcw;
-  }
-  if (use_lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_takahashi_vjp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return ASVGP_ERR_LDS_CAPACITY; }
-  }
-  hipLaunchKernelGGL(band_takahashi_vjp_kernel, dim3(1), dim3(256), use_lds ? bytes : 0, as_stream(stream), L, S, Sbar, Lbar, work, (int)M, k, use_lds);
-  return check_launch("inverse_from_cholesky_band_vjp");
-}
+// the four band operators' launch plan, launchers and entries (and asvgp_band_launch_plan_host)
+#include "band_launch.hpp"
 
 extern "C" int asvgp_band_outer_product(const double* U, const double* V, int64_t M, int64_t D, int k, double sign, double* out, asvgp_stream_t stream) {
   if (!U || !V || !out || M < 1 || D < 1 || k < 0 || k > ASVGP_MAX_BANDWIDTH) { set_error("band_outer_product: bad argument"); return ASVGP_ERR_BAD_ARG; }

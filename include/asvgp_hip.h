@@ -277,6 +277,18 @@ int asvgp_cholesky_band_vjp(const double* L, const double* Lbar, double* Kbar, d
 int asvgp_inverse_from_cholesky_band_vjp(const double* L, const double* S, const double* Sbar, double* Lbar, double* work, int64_t M,
                                          int k, asvgp_stream_t stream);
 int asvgp_band_outer_product(const double* U, const double* V, int64_t M, int64_t D, int k, double sign, double* out, asvgp_stream_t stream);
+/* Host-only: the launch plan of asvgp_cholesky_band (op = 0), asvgp_inverse_from_cholesky_band (1), asvgp_cholesky_band_vjp (2) or
+ * asvgp_inverse_from_cholesky_band_vjp (3) for a band of M columns and bandwidth k, as the entries themselves compute it before they
+ * launch anything - no device.  The entries read the environment once, at their first call; here it is an argument: lds = 0 is
+ * ASVGP_BAND_OPS_LDS=0, seg_blocks = n is ASVGP_BAND_OPS_SEG_BLOCKS=n (0: none; the forward operators take n >= 1, the adjoints n >= 2).
+ * plan8: [0] status, [1] kernel: 0 = the 64-thread register-window sweep (forward operators), 1 = streamed (lane-uniform register
+ * windows, the band through the LDS in segments), 2 = the wave-parallel adjoint, 3 = the sequential adjoint sweep, [2] threads of the one
+ * workgroup, [3] dynamic LDS bytes (never more than 160 KiB), [4] streamed: blocks of k+1 (inverse: k) columns per segment, [5] streamed:
+ * columns (inverse's adjoint: rows) the LDS holds, [6] streamed inverse's adjoint: doubles of its factor array, [7] sequential: 1 = its
+ * two arrays are in the LDS, 0 = in global memory.  Fields that do not belong to the kernel are 0.
+ * Returns the status: ASVGP_OK, ASVGP_ERR_BAD_ARG (plan8 NULL, unknown op) or ASVGP_ERR_UNSUPPORTED (k outside 1..8, M outside
+ * 1..2^30 - 1).  For the CPU tests. */
+int asvgp_band_launch_plan_host(int op, int64_t M, int k, int lds, int seg_blocks, int64_t* plan8);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused ELBO + gradient   replaces GPR_1d.elbo gpr.py:49-89 and the TF reverse-mode pass through the

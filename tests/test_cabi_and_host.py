@@ -619,6 +619,97 @@ def test_phi_launch_plan_follows_the_documented_rules(lib):
     assert refused(algo=2) == BAD_ARG and refused(wg=257) == BAD_ARG and refused(D=0) == BAD_ARG
 
 
+BAND_FIELDS = ("status", "kernel", "threads", "lds", "seg", "cap", "cap_fq", "arrays_in_lds")   # plan8 of asvgp_band_launch_plan_host
+CHOL, INVERSE, CHOL_VJP, INVERSE_VJP = range(4)                                                 # its op
+SWEEP, STREAMED, WAVE, SEQUENTIAL = range(4)                                                    # plan8[1]
+
+
+def _band_plan(lib, op, M, k=4, lds=1, seg_blocks=0):
+    out = np.full(8, -99, dtype=np.int64)
+    rc = lib.asvgp_band_launch_plan_host(op, M, k, lds, seg_blocks, out.ctypes.data)
+    p = dict(zip(BAND_FIELDS, (int(v) for v in out)))
+    assert p["status"] == rc
+    return rc, p
+
+
+def test_band_launch_plan_follows_the_documented_rules(lib):
+    """asvgp_band_launch_plan_host is the plan_band_op that asvgp_cholesky_band, asvgp_inverse_from_cholesky_band and their two adjoints
+    call before they launch anything (csrc/band_launch.hpp), with the two environment variables as arguments.  Every row is written down
+    from the rules ("Which kernel an operator call runs"): W = k + 1; the forward operators divide 156 KiB by 8 W bytes per
+    column (k = 4: 3993 columns; segments of (3993 - W) / W = 797 blocks of W columns, the inverse (3993 - 1) / k = 998 blocks of k), the
+    Cholesky adjoint 160 KiB by 16 W (k = 4: 2048; (2048 - W) / W = 408 blocks), the inverse's adjoint holds seg W + W rows and
+    seg W^2 + 1 factor doubles (k = 4: ((20479 / 5) - 5) / 10 = 409 blocks).  A row lists every field the plan fills for its kernel; the
+    others are 0."""
+    def plan(op, M, **kw):
+        rc, p = _band_plan(lib, op, M, **kw)
+        assert rc == OK, lib.asvgp_last_error_string()
+        assert 0 <= p["lds"] <= LDS_MAX
+        return (p["kernel"], p["threads"], p["seg"], p["cap"], p["cap_fq"], p["lds"], p["arrays_in_lds"])
+
+    # cholesky_band, k = 4:        (kernel, threads, seg, cap, cap_fq, bytes, arrays_in_lds)
+    assert plan(CHOL, 5) == (SWEEP, 64, 0, 0, 0, 0, 0)                      # M = k + 1: nothing beyond the register window
+    assert plan(CHOL, 6) == (STREAMED, 256, 2, 6, 0, 240, 0)
+    assert plan(CHOL, 3993) == (STREAMED, 256, 799, 3993, 0, 159720, 0)     # the last M in one segment
+    assert plan(CHOL, 3994) == (STREAMED, 256, 797, 3993, 0, 159720, 0)
+    assert plan(CHOL, 100, seg_blocks=2) == (STREAMED, 256, 2, 15, 0, 600, 0)
+    assert plan(CHOL, 100, seg_blocks=1) == (STREAMED, 256, 1, 10, 0, 400, 0)
+    assert plan(CHOL, 100, seg_blocks=20) == plan(CHOL, 100) == (STREAMED, 256, 20, 100, 0, 4000, 0)   # an override only shortens
+    for M in (1, 5, 6, 100, 3994, 20000):
+        assert plan(CHOL, M, lds=0) == (SWEEP, 64, 0, 0, 0, 0, 0), M
+    # inverse_from_cholesky_band, k = 4
+    assert plan(INVERSE, 9) == (SWEEP, 64, 0, 0, 0, 0, 0)
+    assert plan(INVERSE, 10) == (STREAMED, 256, 3, 10, 0, 400, 0)
+    assert plan(INVERSE, 3994) == (STREAMED, 256, 998, 3993, 0, 159720, 0)
+    assert plan(INVERSE, 100, seg_blocks=2) == (STREAMED, 256, 2, 9, 0, 360, 0)
+    assert plan(INVERSE, 3994, lds=0) == (SWEEP, 64, 0, 0, 0, 0, 0)
+    # cholesky_band_vjp
+    assert plan(CHOL_VJP, 10) == (WAVE, 256, 0, 0, 0, 800, 0)               # M = 2 (k + 1)
+    assert plan(CHOL_VJP, 11) == (STREAMED, 256, 3, 11, 0, 880, 0)
+    assert plan(CHOL_VJP, 2048) == (STREAMED, 256, 410, 2048, 0, 163840, 0)
+    assert plan(CHOL_VJP, 2049) == (STREAMED, 256, 408, 2048, 0, 163840, 0)
+    assert plan(CHOL_VJP, 100, seg_blocks=1) == (STREAMED, 256, 20, 100, 0, 8000, 0)   # the adjoints take an override from 2 on: 1 is ignored
+    assert plan(CHOL_VJP, 100, seg_blocks=2) == (STREAMED, 256, 2, 15, 0, 1200, 0)
+    assert plan(CHOL_VJP, 18, k=8) == (SEQUENTIAL, 256, 0, 0, 0, 2592, 1)   # M = 2 (k + 1), and 81 lanes are no wave
+    assert plan(CHOL_VJP, 19, k=8) == (STREAMED, 256, 3, 19, 0, 2736, 0)
+    assert plan(CHOL_VJP, 1138, k=8) == (STREAMED, 256, 125, 1137, 0, 163728, 0)
+    assert plan(CHOL_VJP, 2048, lds=0) == (WAVE, 256, 0, 0, 0, 163840, 0)
+    assert plan(CHOL_VJP, 3000, lds=0) == (SEQUENTIAL, 256, 0, 0, 0, 0, 0)
+    # inverse_from_cholesky_band_vjp
+    assert plan(INVERSE_VJP, 10) == (WAVE, 256, 0, 0, 0, 800, 0)
+    assert plan(INVERSE_VJP, 11) == (STREAMED, 256, 3, 11, 55, 880, 0)
+    assert plan(INVERSE_VJP, 2048) == (STREAMED, 256, 410, 2048, 10240, 163840, 0)
+    assert plan(INVERSE_VJP, 2049) == (STREAMED, 256, 409, 2050, 10226, 163808, 0)
+    assert plan(INVERSE_VJP, 100, seg_blocks=2) == (STREAMED, 256, 2, 15, 51, 1008, 0)
+    assert plan(INVERSE_VJP, 100, seg_blocks=1) == plan(INVERSE_VJP, 100) == (STREAMED, 256, 20, 100, 500, 8000, 0)
+    assert plan(INVERSE_VJP, 3000, k=6) == (STREAMED, 256, 208, 1463, 10193, 163472, 0)   # the widest band with the streamed form
+    assert plan(INVERSE_VJP, 300, k=7) == (WAVE, 256, 0, 0, 0, 38400, 0)
+    assert plan(INVERSE_VJP, 1280, k=7) == (WAVE, 256, 0, 0, 0, 163840, 0)
+    assert plan(INVERSE_VJP, 1281, k=7) == (SEQUENTIAL, 256, 0, 0, 0, 0, 0)
+    assert plan(INVERSE_VJP, 18, k=8) == (SEQUENTIAL, 256, 0, 0, 0, 2592, 1)
+    assert plan(INVERSE_VJP, 19, k=8) == (SEQUENTIAL, 256, 0, 0, 0, 2736, 1)
+    assert plan(INVERSE_VJP, 1137, k=8) == (SEQUENTIAL, 256, 0, 0, 0, 163728, 1)
+    assert plan(INVERSE_VJP, 1138, k=8) == (SEQUENTIAL, 256, 0, 0, 0, 0, 0)
+    assert plan(INVERSE_VJP, 2048, lds=0) == (WAVE, 256, 0, 0, 0, 163840, 0)
+    # the forward operators' two segments at their smallest M, k = 8: 159744 / 72 = 2218 columns
+    assert plan(CHOL, 2218, k=8) == (STREAMED, 256, 247, 2218, 0, 159696, 0)
+    assert plan(CHOL, 2219, k=8) == (STREAMED, 256, 245, 2218, 0, 159696, 0)
+    assert plan(INVERSE, 2219, k=8) == (STREAMED, 256, 277, 2218, 0, 159696, 0)
+    # no plan asks for more than the 160 KiB a workgroup gets, whatever the override (a sparse walk; 1 <= M <= 20000 was walked exhaustively
+    # against the previous launch code when the plan was written)
+    for op in range(4):
+        for k in range(1, 9):
+            for M in list(range(1, 60)) + list(range(60, 20000, 97)) + [20000, 10 ** 6, 2 ** 30 - 1]:
+                for sb in (0, 1, 2, 3):
+                    plan(op, M, k=k, seg_blocks=sb)
+    # argument checks of the entry itself
+    assert lib.asvgp_band_launch_plan_host(CHOL, 64, 4, 1, 0, None) == BAD_ARG
+    assert _band_plan(lib, 4, 64)[0] == BAD_ARG and _band_plan(lib, -1, 64)[0] == BAD_ARG
+    for k in (0, 9):
+        assert _band_plan(lib, CHOL, 64, k=k)[0] == UNSUPPORTED and b"bandwidth %d" % k in lib.asvgp_last_error_string()
+    for M in (0, -5, 2 ** 30):
+        assert _band_plan(lib, INVERSE_VJP, M)[0] == UNSUPPORTED and b"M = %d" % M in lib.asvgp_last_error_string()
+
+
 def test_two_sided_factorisation_layout_invariants():
     """asvgp_amd.kronecker.twisted_layout (host logic of GPR_kron's two-sided band Cholesky): for every size both systems have nb super-blocks,
     the separator is their last block, paddings are non-negative, the interiors do not overlap and together with the separator cover

@@ -1788,6 +1788,66 @@ def test_operator_vjps_beyond_the_lds_capacity_walk_the_band_in_segments(A, M, k
     assert np.max(np.abs(Lt.grad.cpu().numpy() - ref)) <= 1e-11 * np.max(np.abs(ref))
 
 
+# (k, M) -> what asvgp_band_launch_plan_host (lds = 1, seg_blocks = 0) must say of cholesky_band, inverse_from_cholesky_band and their two
+# adjoints: "sweep" | "streamed:<segments>" | "wave" | "sequential:lds" | "sequential:global"
+BAND_PLAN_CASES = [
+    ((4, 5), ("sweep", "sweep", "wave", "wave")),                                      # forward sweep against streamed
+    ((4, 6), ("streamed:1", "sweep", "wave", "wave")),
+    ((4, 9), ("streamed:1", "sweep", "wave", "wave")),                                 # inverse sweep against streamed, adjoints wave
+    ((4, 10), ("streamed:1", "streamed:1", "wave", "wave")),                           # against streamed, at the boundary
+    ((4, 11), ("streamed:1", "streamed:1", "streamed:1", "streamed:1")),
+    ((8, 18), ("streamed:1", "streamed:1", "sequential:lds", "sequential:lds")),       # both adjoints sequential at the guard's edge
+    ((8, 19), ("streamed:1", "streamed:1", "streamed:1", "sequential:lds")),           # the first shape past that guard
+    ((7, 300), ("streamed:1", "streamed:1", "streamed:1", "wave")),                    # inverse adjoint wave-parallel
+    ((7, 1281), ("streamed:1", "streamed:1", "streamed:2", "sequential:global")),      # its two arrays no longer fit the LDS
+    ((8, 1138), ("streamed:1", "streamed:1", "streamed:2", "sequential:global")),      # cholesky adjoint: the smallest two segments at k = 8
+    ((8, 2219), ("streamed:2", "streamed:2", "streamed:2", "sequential:global")),      # forward: two segments, cap = 159744 / 72 = 2218
+]
+
+
+@pytest.mark.parametrize("case,branches", BAND_PLAN_CASES)
+def test_band_launch_plan_branches_at_their_smallest_shapes(A, case, branches):
+    """The band launch plan's branches at their smallest shapes (csrc/band_launch.hpp): asvgp_band_launch_plan_host names the branch each
+    of the four operators takes for (k, M), and the real operators (banded.py, autograd) on the diagonally dominant band of the test
+    above agree with the oracle's sweeps: L and S to 1e-12 of the largest entry, the two adjoints to 1e-11."""
+    from asvgp_amd import _lib, banded as Bd
+    lib = _lib.get_lib()
+    k, M = case
+    for op, want in enumerate(branches):
+        p = np.full(8, -99, dtype=np.int64)
+        assert lib.asvgp_band_launch_plan_host(op, M, k, 1, 0, p.ctypes.data) == 0, lib.asvgp_last_error_string()
+        nblk = -(-M // (k if op == 1 else k + 1))             # blocks of k+1 columns, the inverse: of k
+        got = ("sweep", "streamed:%d" % -(-nblk // max(int(p[4]), 1)), "wave", "sequential:%s" % ("lds" if p[7] else "global"))[int(p[1])]
+        assert got == want, (op, k, M, p)
+        assert p[3] <= 160 * 1024
+    rng = np.random.default_rng(M + k)
+    lower = np.zeros((k + 1, M))
+    for d in range(k + 1):
+        lower[d, :M - d] = rng.normal(size=M - d) * (0.3 ** d)
+    dom = np.sum(np.abs(lower[1:]), axis=0)
+    for d in range(1, k + 1):
+        dom[d:] += np.abs(lower[d, :M - d])
+    lower[0] = np.abs(lower[0]) + dom + 0.5                  # strictly diagonally dominant: positive definite
+    L = O.cholesky_band(lower)
+    S = O.inverse_from_cholesky_band(L)
+    Lbar, Sbar = np.zeros((k + 1, M)), np.zeros((k + 1, M))
+    for d in range(k + 1):
+        Lbar[d, :M - d] = rng.normal(size=M - d)
+        Sbar[d, :M - d] = rng.normal(size=M - d)
+    Kt = dev(lower).requires_grad_(True)
+    Lg = Bd.cholesky_band(Kt)
+    assert np.max(np.abs(Lg.detach().cpu().numpy() - L)) <= 1e-12 * np.max(np.abs(L))
+    (Lg * dev(Lbar)).sum().backward()
+    ref = O.cholesky_band_vjp(L, Lbar)
+    assert np.max(np.abs(Kt.grad.cpu().numpy() - ref)) <= 1e-11 * np.max(np.abs(ref))
+    Lt = dev(L).requires_grad_(True)
+    Sg = Bd.inverse_from_cholesky_band(Lt)
+    assert np.max(np.abs(Sg.detach().cpu().numpy() - S)) <= 1e-12 * np.max(np.abs(S))
+    (Sg * dev(Sbar)).sum().backward()
+    ref = O.inverse_from_cholesky_band_vjp(L, S, Sbar)
+    assert np.max(np.abs(Lt.grad.cpu().numpy() - ref)) <= 1e-11 * np.max(np.abs(ref))
+
+
 def test_operator_vjps_vs_oracle_and_reference_style_bound_backpropagates(A):
     """banded_matrices registers gradients for cholesky_band, inverse_from_cholesky_band, solve_triang_mat and product_band_band; the
     reference's optimiser differentiates GPR_1d.elbo through them (gpr.py:56-87, example.py:31-32).  (i) each C-ABI VJP against the
