@@ -1517,34 +1517,6 @@ extern "C" size_t asvgp_kron_stats_doubles(int64_t m1, int64_t m2, int k) {
     default: { constexpr int K = 6; CALL; } break;               \
   }
 
-extern "C" int asvgp_phi_accumulate_kron2d(const double* X, const double* y, int64_t N, const double* mesh1,
-                                           int64_t n_mesh1, double delta1, int64_t m1, const double* mesh2,
-                                           int64_t n_mesh2, double delta2, int64_t m2, int order, double* stats,
-                                           asvgp_stream_t stream) {
-  if ((N > 0 && (!X || !y)) || !mesh1 || !mesh2 || !stats || N < 0 || !(delta1 > 0) || !(delta2 > 0) ||
-      n_mesh1 != m1 - order + 1 || n_mesh2 != m2 - order + 1) {
-    set_error("phi_accumulate_kron2d: bad argument");
-    return ASVGP_ERR_BAD_ARG;
-  }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("phi_accumulate_kron2d: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  if ((reinterpret_cast<uintptr_t>(X) & 15) != 0) { set_error("phi_accumulate_kron2d: X must be 16-byte aligned (N,2) row-major"); return ASVGP_ERR_BAD_ARG; }
-  hipStream_t st = as_stream(stream);
-  const size_t nd = asvgp_kron_stats_doubles(m1, m2, order);
-  hipError_t e = hipMemsetAsync(stats, 0, nd * sizeof(double), st);
-  if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return ASVGP_ERR_HIP; }
-  if (N == 0) return ASVGP_OK;
-  const long Mtot = (long)m1 * m2;
-  double* Ablk = stats;
-  double* rhs = stats + (size_t)kron_noff(order) * Mtot;
-  double* yy = rhs + Mtot;
-  long blocks = (N + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  KRON_DISPATCH(order, hipLaunchKernelGGL(phi_kron2d_kernel<K>, dim3((unsigned)blocks), dim3(256), 0, st, X, y, (long)N, mesh1,
-                                          (int)n_mesh1, 1.0 / delta1, (int)m1, mesh2, (int)n_mesh2, 1.0 / delta2, (int)m2,
-                                          Ablk, rhs, yy));
-  return check_launch("phi_accumulate_kron2d");
-}
-
 extern "C" int asvgp_kron_evaluate_2d(const double* X, int64_t N, const double* mesh1, int64_t n_mesh1, double delta1,
                                       const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
                                       int64_t* rows, double* data, asvgp_stream_t stream) {
@@ -1834,89 +1806,6 @@ extern "C" int asvgp_kron_cell_index(const double* X, int64_t N, const double* m
   return check_launch("kron_cell_index");
 }
 
-template <typename TIN>
-static int phi_accumulate_kron2d_sorted_entry(const TIN* Xs, const TIN* ys, int64_t N, const int64_t* cell_start,
-                                                  const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
-                                                  const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
-                                                  double* stats, asvgp_stream_t stream) {
-  if ((N > 0 && (!Xs || !ys)) || !cell_start || !mesh1 || !mesh2 || !stats || N < 0 || !(delta1 > 0) || !(delta2 > 0) ||
-      n_mesh1 != m1 - order + 1 || n_mesh2 != m2 - order + 1 || n_mesh1 < 2 || n_mesh2 < 2) {
-    set_error("phi_accumulate_kron2d_sorted: bad argument");
-    return ASVGP_ERR_BAD_ARG;
-  }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("phi_accumulate_kron2d_sorted: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  if ((reinterpret_cast<uintptr_t>(Xs) & (2 * sizeof(TIN) - 1)) != 0) { set_error("phi_accumulate_kron2d_sorted: Xs must be aligned to one (x1, x2) pair, (N,2) row-major"); return ASVGP_ERR_BAD_ARG; }
-  hipStream_t st = as_stream(stream);
-  const size_t nd = asvgp_kron_stats_doubles(m1, m2, order);
-  hipError_t e = hipSuccess;
-  if (N == 0) {
-    e = hipMemsetAsync(stats, 0, nd * sizeof(double), st);
-    if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return ASVGP_ERR_HIP; }
-    return ASVGP_OK;
-  }
-  const long Mtot = (long)m1 * m2;
-  double* Ablk = stats;
-  double* rhs = stats + (size_t)kron_noff(order) * Mtot;
-  double* yy = rhs + Mtot;
-  const long ncell = (long)(n_mesh1 - 1) * (n_mesh2 - 1);
-  static const bool use_atomics_env = getenv("ASVGP_KRON_PHI_ATOMICS") && atoi(getenv("ASVGP_KRON_PHI_ATOMICS")) != 0;   // (the round-1..3 kernel, for comparison)
-  const bool use_atomics = use_atomics_env && sizeof(TIN) == sizeof(double);
-  const long ncell_pad = (ncell + KRON_STRIP - 1) / KRON_STRIP * KRON_STRIP;
-  double* cellsum = nullptr;
-  if (!use_atomics) {
-    size_t nout = 0;
-    KRON_DISPATCH(order, { nout = (size_t)KronOut<K>::NOUT; });
-    if (hipMallocAsync(reinterpret_cast<void**>(&cellsum), nout * (size_t)ncell_pad * sizeof(double), st) != hipSuccess) {
-      (void)hipGetLastError();
-      cellsum = nullptr;                              // (no room for the staging buffer: the atomic kernel needs none)
-    }
-  }
-  e = cellsum ? hipMemsetAsync(yy, 0, sizeof(double), st)            // (the gather overwrites every band and rhs entry)
-              : hipMemsetAsync(stats, 0, nd * sizeof(double), st);
-  if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); if (cellsum) (void)hipFreeAsync(cellsum, st); return ASVGP_ERR_HIP; }
-  if (cellsum) {
-    const long strips = ncell_pad / KRON_STRIP;
-    static const long kgrid = getenv("ASVGP_KRON_PHI_GRID") ? atol(getenv("ASVGP_KRON_PHI_GRID")) : 512;   // resident workgroups: each walks several strips, the next cell's points in flight
-    const long total = (long)(kron_noff(order) + 1) * Mtot;
-    long gblocks = (total + 255) / 256;
-    if (gblocks > 8192) gblocks = 8192;
-    KRON_DISPATCH(order, {
-      hipLaunchKernelGGL((phi_kron2d_mfma_kernel<K, TIN>), dim3((unsigned)(strips < kgrid ? strips : kgrid)), dim3(64 * KRON_STRIP), 0, st, Xs, ys,
-                         reinterpret_cast<const long long*>(cell_start), (int)ncell, (int)ncell_pad, mesh1, 1.0 / delta1, mesh2,
-                         (int)n_mesh2, 1.0 / delta2, cellsum, yy);
-      hipLaunchKernelGGL(phi_kron2d_gather_kernel<K>, dim3((unsigned)gblocks), dim3(256), 0, st, cellsum, (int)ncell_pad, (int)(n_mesh1 - 1),
-                         (int)(n_mesh2 - 1), (int)m1, (int)m2, Ablk, rhs);
-    });
-    (void)hipFreeAsync(cellsum, st);
-    return check_launch("phi_accumulate_kron2d_sorted (matrix-core cell sums + gather)");
-  }
-  if constexpr (sizeof(TIN) != sizeof(double)) {
-    set_error("phi_accumulate_kron2d_sorted_f32: no room for the staging buffer (%ld cells)", ncell);
-    return ASVGP_ERR_HIP;
-  } else {
-  long blocks = ncell < 4096 ? ncell : 4096;
-  KRON_DISPATCH(order, {
-    hipLaunchKernelGGL(phi_kron2d_cells_kernel<K>, dim3((unsigned)blocks), dim3(256), 0, st, Xs, ys,
-                       reinterpret_cast<const long long*>(cell_start), (int)ncell, mesh1, 1.0 / delta1, (int)m1, mesh2,
-                       (int)n_mesh2, 1.0 / delta2, (int)m2, Ablk, rhs, yy);
-  });
-  return check_launch("phi_accumulate_kron2d_sorted");
-  }
-}
-
-extern "C" int asvgp_phi_accumulate_kron2d_sorted(const double* Xs, const double* ys, int64_t N, const int64_t* cell_start,
-                                                  const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
-                                                  const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
-                                                  double* stats, asvgp_stream_t stream) {
-  return phi_accumulate_kron2d_sorted_entry<double>(Xs, ys, N, cell_start, mesh1, n_mesh1, delta1, m1, mesh2, n_mesh2, delta2, m2, order, stats, stream);
-}
-
-// fp32 STORAGE of the cell-sorted points (BASELINE config 4): 12 B per point streamed, widened exactly, fp64 arithmetic
-extern "C" int asvgp_phi_accumulate_kron2d_sorted_f32(const float* Xs, const float* ys, int64_t N, const int64_t* cell_start,
-                                                      const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
-                                                      const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
-                                                      double* stats, asvgp_stream_t stream) {
-  return phi_accumulate_kron2d_sorted_entry<float>(Xs, ys, N, cell_start, mesh1, n_mesh1, delta1, m1, mesh2, n_mesh2, delta2, m2, order, stats, stream);
-}
-
+// (the five Phi-pass entries: kron_phi_launch.hpp)
 #include "kron_weighted.hpp"
+#include "kron_phi_launch.hpp"

@@ -1,6 +1,7 @@
 // Weighted Khatri-Rao Phi pass (d = 2): A_w = Phi W Phi^T as the same block band, b_w = Phi W y, yy_w = sum w y^2 in the layout of
 // asvgp_phi_accumulate_kron2d, plus wstats = [sum w, sum_{w>0} log w, #{w > 0}].  (Included by kron.hip behind the unweighted kernels,
-// whose code it does not touch; the cell-sorted form shares phi_kron2d_gather_kernel.)
+// whose code it does not touch; the cell-sorted form shares phi_kron2d_gather_kernel.  Kernels only: the host side of both entries is
+// kron_phi_launch.hpp.)
 //   per point (asvgp_phi_accumulate_kron2d_weighted):   phi_kron2d_kernel with every product scaled by w; a row with w = 0 is skipped.
 //   cell-sorted (asvgp_phi_accumulate_kron2d_sorted_weighted): a cell's share is Phi_c^T diag(w) Phi_c - the A operand of the
 //     v_mfma_f64_16x16x4 products is w phi, the B operand phi; w travels beside (x, y) through the wave's LDS buffer (32 B per point).
@@ -225,81 +226,3 @@ __global__ __launch_bounds__(64 * KRON_STRIP) void phi_kron2d_mfma_weighted_kern
 }
 
 }  // namespace asvgp
-
-using namespace asvgp;
-
-extern "C" int asvgp_phi_accumulate_kron2d_weighted(const double* X, const double* y, const double* w, int64_t N, const double* mesh1,
-                                                    int64_t n_mesh1, double delta1, int64_t m1, const double* mesh2,
-                                                    int64_t n_mesh2, double delta2, int64_t m2, int order, double* stats, double* wstats,
-                                                    asvgp_stream_t stream) {
-  if ((N > 0 && (!X || !y || !w)) || !mesh1 || !mesh2 || !stats || !wstats || N < 0 || !(delta1 > 0) || !(delta2 > 0) ||
-      n_mesh1 != m1 - order + 1 || n_mesh2 != m2 - order + 1 || n_mesh1 < 2 || n_mesh2 < 2) {
-    set_error("phi_accumulate_kron2d_weighted: bad argument");
-    return ASVGP_ERR_BAD_ARG;
-  }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("phi_accumulate_kron2d_weighted: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  if ((reinterpret_cast<uintptr_t>(X) & 15) != 0) { set_error("phi_accumulate_kron2d_weighted: X must be 16-byte aligned (N,2) row-major"); return ASVGP_ERR_BAD_ARG; }
-  hipStream_t st = as_stream(stream);
-  const size_t nd = asvgp_kron_stats_doubles(m1, m2, order);
-  hipError_t e = hipMemsetAsync(stats, 0, nd * sizeof(double), st);
-  if (e == hipSuccess) e = hipMemsetAsync(wstats, 0, 3 * sizeof(double), st);
-  if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return ASVGP_ERR_HIP; }
-  if (N == 0) return ASVGP_OK;
-  const long Mtot = (long)m1 * m2;
-  double* Ablk = stats;
-  double* rhs = stats + (size_t)kron_noff(order) * Mtot;
-  double* yy = rhs + Mtot;
-  long blocks = (N + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  KRON_DISPATCH(order, hipLaunchKernelGGL(phi_kron2d_weighted_kernel<K>, dim3((unsigned)blocks), dim3(256), 0, st, X, y, w, (long)N, mesh1,
-                                          (int)n_mesh1, 1.0 / delta1, (int)m1, mesh2, (int)n_mesh2, 1.0 / delta2, (int)m2,
-                                          Ablk, rhs, yy, wstats));
-  return check_launch("phi_accumulate_kron2d_weighted");
-}
-
-extern "C" int asvgp_phi_accumulate_kron2d_sorted_weighted(const double* Xs, const double* ys, const double* ws, int64_t N, const int64_t* cell_start,
-                                                           const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
-                                                           const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
-                                                           double* stats, double* wstats, asvgp_stream_t stream) {
-  if ((N > 0 && (!Xs || !ys || !ws)) || !cell_start || !mesh1 || !mesh2 || !stats || !wstats || N < 0 || !(delta1 > 0) || !(delta2 > 0) ||
-      n_mesh1 != m1 - order + 1 || n_mesh2 != m2 - order + 1 || n_mesh1 < 2 || n_mesh2 < 2) {
-    set_error("phi_accumulate_kron2d_sorted_weighted: bad argument");
-    return ASVGP_ERR_BAD_ARG;
-  }
-  if (order < 1 || order > ASVGP_MAX_ORDER) { set_error("phi_accumulate_kron2d_sorted_weighted: order %d unsupported", order); return ASVGP_ERR_UNSUPPORTED; }
-  if ((reinterpret_cast<uintptr_t>(Xs) & 15) != 0) { set_error("phi_accumulate_kron2d_sorted_weighted: Xs must be 16-byte aligned (N,2) row-major"); return ASVGP_ERR_BAD_ARG; }
-  hipStream_t st = as_stream(stream);
-  const size_t nd = asvgp_kron_stats_doubles(m1, m2, order);
-  const long Mtot = (long)m1 * m2;
-  double* Ablk = stats;
-  double* rhs = stats + (size_t)kron_noff(order) * Mtot;
-  double* yy = rhs + Mtot;
-  hipError_t e = hipMemsetAsync(wstats, 0, 3 * sizeof(double), st);
-  if (e == hipSuccess) e = N == 0 ? hipMemsetAsync(stats, 0, nd * sizeof(double), st) : hipMemsetAsync(yy, 0, sizeof(double), st);   // (the gather overwrites every band and rhs entry)
-  if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return ASVGP_ERR_HIP; }
-  if (N == 0) return ASVGP_OK;
-  const long ncell = (long)(n_mesh1 - 1) * (n_mesh2 - 1);
-  const long ncell_pad = (ncell + KRON_STRIP - 1) / KRON_STRIP * KRON_STRIP;
-  size_t nout = 0;
-  KRON_DISPATCH(order, { nout = (size_t)KronOut<K>::NOUT; });
-  double* cellsum = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void**>(&cellsum), nout * (size_t)ncell_pad * sizeof(double), st) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("phi_accumulate_kron2d_sorted_weighted: no room for the staging buffer (%ld cells); the per-point entry needs none", ncell);
-    return ASVGP_ERR_HIP;
-  }
-  const long strips = ncell_pad / KRON_STRIP;
-  const long kgrid = 512;                                          // resident workgroups, as the unweighted launch
-  const long total = (long)(kron_noff(order) + 1) * Mtot;
-  long gblocks = (total + 255) / 256;
-  if (gblocks > 8192) gblocks = 8192;
-  KRON_DISPATCH(order, {
-    hipLaunchKernelGGL((phi_kron2d_mfma_weighted_kernel<K>), dim3((unsigned)(strips < kgrid ? strips : kgrid)), dim3(64 * KRON_STRIP), 0, st, Xs, ys, ws,
-                       reinterpret_cast<const long long*>(cell_start), (int)ncell, (int)ncell_pad, mesh1, 1.0 / delta1, mesh2,
-                       (int)n_mesh2, 1.0 / delta2, cellsum, yy, wstats);
-    hipLaunchKernelGGL(phi_kron2d_gather_kernel<K>, dim3((unsigned)gblocks), dim3(256), 0, st, cellsum, (int)ncell_pad, (int)(n_mesh1 - 1),
-                       (int)(n_mesh2 - 1), (int)m1, (int)m2, Ablk, rhs);
-  });
-  (void)hipFreeAsync(cellsum, st);
-  return check_launch("phi_accumulate_kron2d_sorted_weighted (matrix-core cell sums + gather)");
-}

@@ -592,7 +592,8 @@ int asvgp_predict_kron2d(const double* Xnew, int64_t n, const double* mesh1, int
  * entry-major into a stream-ordered staging buffer (152 doubles per cell at k = 3, 350 at k = 4; hipMallocAsync on `stream`)
  * and a gather kernel forms every output from the <= (k+1)^2 cells that touch it: no statistic atomics, deterministic sums.
  * (ASVGP_KRON_PHI_ATOMICS=1 in the environment, or no room for the staging buffer: the per-cell kernel with one global atomic per
- * block-band entry and cell.) */
+ * block-band entry and cell - this entry alone has one.  ASVGP_KRON_PHI_GRID=n: at most n resident workgroups of the matrix-core
+ * kernel, here and in the fp32-storage and weighted entries below; default 512, a value below 1 is 1.) */
 int asvgp_kron_cell_index(const double* X, int64_t N, const double* mesh1, int64_t n_mesh1, double delta1,
                           const double* mesh2, int64_t n_mesh2, double delta2, int* cell, asvgp_stream_t stream);
 int asvgp_phi_accumulate_kron2d_sorted(const double* Xs, const double* ys, int64_t N, const int64_t* cell_start,
@@ -620,6 +621,19 @@ int asvgp_phi_accumulate_kron2d_sorted_weighted(const double* Xs, const double* 
                                                 const double* mesh1, int64_t n_mesh1, double delta1, int64_t m1,
                                                 const double* mesh2, int64_t n_mesh2, double delta2, int64_t m2, int order,
                                                 double* stats, double* wstats, asvgp_stream_t stream);
+/* Host-only: the launch plan of the five asvgp_phi_accumulate_kron2d* entries above, as they compute it themselves before they allocate,
+ * clear or launch anything - no device.  sorted = 0: the per-point entries, 1: the cell-sorted ones; weighted, f32: which of them (f32
+ * with sorted = 1, weighted = 0 only).  The entries read the environment once, at their first call; here it is an argument: atomics
+ * is ASVGP_KRON_PHI_ATOMICS, grid is ASVGP_KRON_PHI_GRID (512 where it is not set).  staging = 0: the plan for a call whose staging
+ * buffer found no room.  plan12: [0] status, [1] kernel: 0 = none (N = 0), 1 = per point, 2 = per cell, 3 = matrix-core cell sums +
+ * gather, [2] its grid, [3] its workgroup, [4] the gather's grid, [5] bytes of the staging buffer, [6] cells of the mesh, [7] cells
+ * rounded up to strips of 8, [8] 1 = all of stats is cleared first, 0 = yy only, [9] doubles in front of rhs and [10] of yy inside
+ * stats, [11] 0.  Fields that do not belong to the kernel are 0.
+ * Returns the status: ASVGP_OK, ASVGP_ERR_BAD_ARG (plan12 NULL, N < 0, n_mesh != m - order + 1, n_mesh < 2, no such entry),
+ * ASVGP_ERR_UNSUPPORTED (order outside 1..6; m1, m2, n_mesh1, n_mesh2 or the cells rounded up to strips do not fit an int) or
+ * ASVGP_ERR_HIP (staging = 0 and the entry has no kernel without the buffer).  For the CPU tests. */
+int asvgp_kron_phi_launch_plan_host(int sorted, int weighted, int f32, int64_t N, int64_t m1, int64_t m2, int64_t n_mesh1, int64_t n_mesh2,
+                                    int order, int atomics, int64_t grid, int staging, int64_t* plan12);
 
 /* Selected inverse of P = Kuu + KufKfu/sigma2 on the band (what the gradient of gpr.py:282-308 and the predictive variance
  * of gpr.py:319-330 need of P^-1), through dense super-blocks of size Bb (a multiple of 32, >= bw): the band factor is

@@ -710,6 +710,132 @@ def test_band_launch_plan_follows_the_documented_rules(lib):
         assert _band_plan(lib, INVERSE_VJP, M)[0] == UNSUPPORTED and b"M = %d" % M in lib.asvgp_last_error_string()
 
 
+KRON_PHI_FIELDS = ("status", "kernel", "grid", "threads", "gather_grid", "staging", "ncell", "ncell_pad", "clear_all", "rhs_off", "yy_off",
+                   "zero")                                                  # plan12 of asvgp_kron_phi_launch_plan_host
+KP_NONE, KP_POINT, KP_CELLS, KP_MFMA = range(4)                             # plan12[1]
+ERR_HIP = -5
+KP_FORMS = {"point": (0, 0, 0), "point_w": (0, 1, 0), "sorted": (1, 0, 0), "sorted_f32": (1, 0, 1), "sorted_w": (1, 1, 0)}   # (sorted, weighted, f32)
+KP_SORTED = ("sorted", "sorted_f32", "sorted_w")
+
+
+def _kron_phi_plan(lib, form, N=1000, mesh=(2, 3), k=1, m=None, atomics=0, grid=512, staging=1):
+    """(status, fields by name) of asvgp_kron_phi_launch_plan_host for a mesh of mesh[0] x mesh[1] knots and order k (m = n_mesh + k - 1)"""
+    m = m or (mesh[0] + k - 1, mesh[1] + k - 1)
+    out = np.full(12, -99, dtype=np.int64)
+    rc = lib.asvgp_kron_phi_launch_plan_host(*KP_FORMS[form], N, m[0], m[1], mesh[0], mesh[1], k, atomics, grid, staging, out.ctypes.data)
+    p = dict(zip(KRON_PHI_FIELDS, (int(v) for v in out)))
+    assert p["status"] == rc and p["zero"] == 0
+    return rc, p
+
+
+def test_kron_phi_launch_plan_follows_the_documented_rules(lib):
+    """asvgp_kron_phi_launch_plan_host is the plan_kron_phi that the five asvgp_phi_accumulate_kron2d* entries call before they allocate,
+    clear or launch anything (csrc/kron_phi_launch.hpp), with the two environment variables and the outcome of the allocation as
+    arguments.  Every row is written down from the rules (the table of the Kronecker Phi pass): stats is
+    [n_off m1 m2 | m1 m2 | 1] with n_off = k (2k + 1) + k + 1 (5 at k = 1, 25 at k = 3, 41 at k = 4); the cells are rounded up to strips of
+    8; a cell leaves 14, 54, 152, 350, 702, 1274 doubles in the staging buffer at k = 1..6; the gather has one thread per (n_off + 1) m1 m2
+    outputs.  A row is (kernel, grid, threads, gather grid, staging bytes, cells, padded cells, clear all, rhs offset, yy offset)."""
+    def plan(form, **kw):
+        rc, p = _kron_phi_plan(lib, form, **kw)
+        assert rc == OK, lib.asvgp_last_error_string()
+        return tuple(p[f] for f in KRON_PHI_FIELDS[1:-1])
+
+    # N = 0 in every form: all of stats is cleared, nothing is launched
+    for form in KP_FORMS:
+        assert plan(form, N=0) == (KP_NONE, 0, 0, 0, 0, 2, 8, 1, 30, 36), form
+        assert plan(form, N=0, atomics=1, staging=0) == (KP_NONE, 0, 0, 0, 0, 2, 8, 1, 30, 36), form
+    # per point: one thread per point, at most 4096 workgroups of 256
+    for N, grid in ((1, 1), (256, 1), (257, 2), (4095 * 256 + 1, 4096), (4096 * 256, 4096), (4096 * 256 + 1, 4096)):
+        for form in ("point", "point_w"):
+            assert plan(form, N=N) == (KP_POINT, grid, 256, 0, 0, 2, 8, 1, 30, 36), (form, N)
+    assert plan("point", atomics=1, grid=7, staging=0) == plan("point") == (KP_POINT, 4, 256, 0, 0, 2, 8, 1, 30, 36)
+    # sorted, 2 x 3 mesh points: 2 cells, one strip of 8, 6 (5 + 1) = 36 gather outputs
+    for form in KP_SORTED:
+        assert plan(form) == (KP_MFMA, 1, 512, 1, 14 * 8 * 8, 2, 8, 0, 30, 36), form
+    # sorted, 66 x 66 mesh points: 4225 cells, pad 4232, 529 strips; 6 * 4356 = 26136 gather outputs = 102.1 workgroups
+    big = dict(mesh=(66, 66))
+    for form in KP_SORTED:
+        assert plan(form, **big) == (KP_MFMA, 512, 512, 103, 14 * 4232 * 8, 4225, 4232, 0, 21780, 26136), form
+        assert [plan(form, grid=g, **big)[1] for g in (600, 529, 528, 1, 0, -5)] == [529, 529, 528, 1, 1, 1], form
+    # the staging buffer: doubles per padded cell (152 and 350 are the figures of asvgp_hip.h)
+    assert [plan("sorted", k=k)[4] // (8 * 8) for k in range(1, 7)] == [14, 54, 152, 350, 702, 1274]
+    assert plan("sorted_w", k=3) == (KP_MFMA, 1, 512, 3, 152 * 8 * 8, 2, 8, 0, 500, 520)          # m = 4 x 5: 26 * 20 = 520 outputs
+    assert plan("sorted_f32", k=4) == (KP_MFMA, 1, 512, 5, 350 * 8 * 8, 2, 8, 0, 1230, 1260)      # m = 5 x 6: 42 * 30 = 1260 outputs
+    # the gather clamp at order 3: 26 m^2 outputs; m = 283: 8134.04 workgroups, 284: 8191.6 -> 8192 (the last grid that is not cut), 285: 8249.4
+    for m, ncell_pad, gather in ((283, 78400, 8135), (284, 78968, 8192), (285, 79528, 8192)):
+        for form in KP_SORTED:
+            assert plan(form, mesh=(m - 2, m - 2), k=3) == (KP_MFMA, 512, 512, gather, 152 * ncell_pad * 8, (m - 3) ** 2, ncell_pad, 0, 25 * m * m,
+                                                            26 * m * m), (form, m)
+    # ASVGP_KRON_PHI_ATOMICS: the per-cell kernel, which only plain fp64 has - one workgroup per cell, at most 4096, all of stats cleared
+    assert plan("sorted", atomics=1) == (KP_CELLS, 2, 256, 0, 0, 2, 8, 1, 30, 36)
+    assert plan("sorted", atomics=1, **big) == (KP_CELLS, 4096, 256, 0, 0, 4225, 4232, 1, 21780, 26136)
+    assert plan("sorted", atomics=1, mesh=(65, 65)) == (KP_CELLS, 4096, 256, 0, 0, 4096, 4096, 1, 21125, 25350)
+    for form in ("sorted_f32", "sorted_w"):
+        assert plan(form, atomics=1, **big) == plan(form, **big), form
+    # no room for the staging buffer: plain fp64 takes the per-cell kernel, the other two refuse
+    assert plan("sorted", staging=0, **big) == plan("sorted", staging=0, atomics=1, **big) == plan("sorted", atomics=1, **big)
+    rc, p = _kron_phi_plan(lib, "sorted_f32", staging=0, **big)
+    assert rc == ERR_HIP and lib.asvgp_last_error_string() == b"phi_accumulate_kron2d_sorted_f32: no room for the staging buffer (4225 cells)"
+    rc, p = _kron_phi_plan(lib, "sorted_w", staging=0, atomics=1, **big)
+    assert rc == ERR_HIP
+    assert lib.asvgp_last_error_string() == b"phi_accumulate_kron2d_sorted_weighted: no room for the staging buffer (4225 cells); the per-point entry needs none"
+    # the refusals of the argument check: nothing but the status is filled
+    def refused(form, **kw):
+        rc, p = _kron_phi_plan(lib, form, **kw)
+        assert rc != OK and not any(p[f] for f in KRON_PHI_FIELDS[1:])
+        assert lib.asvgp_last_error_string().startswith(b"kron_phi_launch_plan_host: ")
+        return rc
+
+    for form in KP_FORMS:
+        for k in (0, 7):
+            assert refused(form, k=k) == UNSUPPORTED and b"order %d unsupported" % k in lib.asvgp_last_error_string(), (form, k)
+        for mesh in ((1, 3), (2, 1), (1, 1)):
+            assert refused(form, mesh=mesh, k=3) == BAD_ARG, (form, mesh)
+        assert refused(form, mesh=(8, 9), k=3, m=(10, 12)) == BAD_ARG and refused(form, mesh=(8, 9), k=3, m=(11, 11)) == BAD_ARG
+        assert refused(form, N=-1) == BAD_ARG
+        assert b"bad argument" in lib.asvgp_last_error_string()
+        # what the kernels take as int: 46341^2 = 2147488281 cells; 2 * 1073741823 = 2^31 - 2 cells fit, their 2^31 padded cells do not
+        assert refused(form, mesh=(46342, 46342)) == UNSUPPORTED and b"2147488281 cells" in lib.asvgp_last_error_string(), form
+        assert refused(form, mesh=(3, 1073741824)) == UNSUPPORTED and b"2147483646 cells" in lib.asvgp_last_error_string(), form
+        assert refused(form, mesh=(2, 2 ** 31 - 1), k=2) == UNSUPPORTED and b"m2 = 2147483648" in lib.asvgp_last_error_string(), form
+        assert refused(form, mesh=(2 ** 31, 2)) == UNSUPPORTED and b"m1 = 2147483648" in lib.asvgp_last_error_string(), form
+        rc, p = _kron_phi_plan(lib, form, mesh=(9, 268435456))               # 8 * 268435455 = 2^31 - 8 cells: whole strips, the most an int holds
+        assert rc == OK and p["ncell"] == p["ncell_pad"] == 2 ** 31 - 8, form
+    assert lib.asvgp_kron_phi_launch_plan_host(1, 0, 0, 1000, 2, 3, 2, 3, 1, 0, 512, 1, None) == BAD_ARG
+    out = np.zeros(12, dtype=np.int64)
+    for sorted_, weighted in ((0, 0), (0, 1), (1, 1)):                       # fp32 storage: the plain sorted entry only
+        assert lib.asvgp_kron_phi_launch_plan_host(sorted_, weighted, 1, 1000, 2, 3, 2, 3, 1, 0, 512, 1, out.ctypes.data) == BAD_ARG
+
+
+KRON_ENTRIES = ("phi_accumulate_kron2d", "phi_accumulate_kron2d_sorted", "phi_accumulate_kron2d_sorted_f32")
+
+
+@pytest.mark.parametrize("name", KRON_ENTRIES)
+def test_accumulate_kron2d_unweighted_argument_checks(lib, name):
+    """The twin of test_accumulate_kron2d_weighted_argument_checks for the three unweighted entries: the same cases, refused on the host
+    with the entry's own name in front - nothing is dereferenced or launched."""
+    FAKE = ctypes.c_void_p(0x1000)
+    ODD = ctypes.c_void_p(0x1004 if name.endswith("f32") else 0x1008)       # off the (x1, x2) pair: 8 bytes of fp32, 16 of fp64
+    sorted_ = "sorted" in name
+
+    def call(X=FAKE, y=FAKE, N=10, start=FAKE, mesh1=FAKE, n1=8, m1=10, mesh2=FAKE, n2=9, m2=11, order=3, stats=FAKE):
+        args = (X, y, N) + ((start,) if sorted_ else ()) + (mesh1, n1, 0.1, m1, mesh2, n2, 0.1, m2, order, stats, None)
+        return getattr(lib, "asvgp_" + name)(*args)
+
+    err = lambda: lib.asvgp_last_error_string().decode()
+    cases = [{"X": None}, {"y": None}, {"mesh1": None}, {"mesh2": None}, {"stats": None}, {"N": -1}, {"n1": 9}, {"n2": 8}, {"X": ODD},
+             {"n1": 1, "m1": 3}, {"n2": 1, "m2": 3}]                        # (a mesh of one knot has no cell)
+    if sorted_:
+        cases.append({"start": None})
+    for kw in cases:
+        assert call(**kw) == BAD_ARG, kw
+        assert err().startswith(name + ": "), (kw, err())
+    assert "aligned" in (call(X=ODD), err())[1]
+    assert call(order=7, n1=4, n2=5) == UNSUPPORTED and err() == name + ": order 7 unsupported"
+    assert call(order=0, n1=11, n2=12) == UNSUPPORTED and err() == name + ": order 0 unsupported"
+    assert call(n1=46342, m1=46344, n2=46342, m2=46344) == UNSUPPORTED and err().startswith(name + ": 2147488281 cells")
+
+
 def test_two_sided_factorisation_layout_invariants():
     """asvgp_amd.kronecker.twisted_layout (host logic of GPR_kron's two-sided band Cholesky): for every size both systems have nb super-blocks,
     the separator is their last block, paddings are non-negative, the interiors do not overlap and together with the separator cover

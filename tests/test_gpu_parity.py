@@ -1589,6 +1589,151 @@ def test_kron_cell_sorted_phi_pass_equals_per_point_pass(A, order, m1, m2, N):
     assert st[-1] == N and np.array_equal(np.bincount(cid, minlength=len(st) - 1), np.diff(st))
 
 
+def _oracle_kron_statistics(order, m1, m2, X, y, w=None):
+    """[block band | Kuf y | y^T y] from the oracle's basis pieces: Kuf is O.make_kvs_sparse of the two design matrices (row i1 m2 + i2),
+    here without its Python loop over the points - the first columns are held to it bit for bit -, then Kuf W Kuf^T, Kuf W y, sum w y^2"""
+    import scipy.sparse as sp
+    n, k1 = X.shape[0], order + 1
+    bs = [O.make_mesh(0, 1, m1, order) + (m1,), O.make_mesh(-1, 2, m2, order) + (m2,)]       # (mesh, delta, m): O.Basis wants m >= 3 for its Gram bands
+    (r1, _, d1), (r2, _, d2) = [O.evaluate_basis_coo(mesh, delta, order, m, X[:, i]) for i, (mesh, delta, m) in enumerate(bs)]
+    r1, d1, r2, d2 = (a.reshape(k1, n) for a in (r1, d1, r2, d2))
+    rows = (r1[:, None, :] * m2 + r2[None, :, :]).reshape(-1)
+    data = (d1[:, None, :] * d2[None, :, :]).reshape(-1)
+    Kuf = sp.csr_matrix((data, (rows, np.tile(np.arange(n), k1 * k1))), shape=(m1 * m2, n))
+    head = O.make_kvs_sparse([O.evaluate_basis(mesh, delta, order, m, X[:200, i]) for i, (mesh, delta, m) in enumerate(bs)])
+    assert abs(Kuf[:, :200] - head).max() == 0.0
+    w = np.ones(n) if w is None else w
+    Asp = (Kuf @ sp.diags(w) @ Kuf.T).tocsr()
+    offs = [(0, d) for d in range(k1)] + [(a, d) for a in range(1, k1) for d in range(-order, k1)]
+    band = np.zeros((len(offs), m1 * m2))
+    i1, i2 = np.divmod(np.arange(m1 * m2), m2)
+    for o, (a, d) in enumerate(offs):
+        c = np.flatnonzero((i1 + a < m1) & (i2 + d >= 0) & (i2 + d < m2))
+        band[o, c] = np.asarray(Asp[c + a * m2 + d, c]).reshape(-1)
+    return np.concatenate([band.reshape(-1), np.asarray(Kuf @ (w * y[:, 0])).reshape(-1), [np.sum(w * y[:, 0] ** 2)]])
+
+
+class _BareKronPhi:
+    """The five entries driven as GPR_kron drives them (_sort_by_cell, _phi_pass_local) on a mesh that no basis object holds: the static
+    Gram bands of basis.py need m >= 3, a mesh of two knots is m = 2 at order 1.  _stats, _wstats, _fp32_storage, phi_pass as the model's."""
+
+    def __init__(self, order, m1, m2, X, y, w=None):
+        from asvgp_amd._lib import get_lib
+        self.lib, self.order, self.m = get_lib(), order, (m1, m2)
+        self.mesh = [dev(O.make_mesh(0, 1, m1, order)[0]), dev(O.make_mesh(-1, 2, m2, order)[0])]
+        self.delta = [float(O.make_mesh(0, 1, m1, order)[1]), float(O.make_mesh(-1, 2, m2, order)[1])]
+        self._fp32_storage = X.dtype == torch.float32
+        self.X, self.y, self.w = X.double().cuda().contiguous(), y.double().cuda().reshape(-1).contiguous(), None if w is None else dev(w)
+        self.noff, self.Mtot = order * (2 * order + 1) + order + 1, m1 * m2
+        self._stats = torch.zeros(self.noff * self.Mtot + self.Mtot + 1, dtype=torch.float64, device="cuda")
+        self._wstats = torch.zeros(3, dtype=torch.float64, device="cuda")
+        n, ncell = self.X.shape[0], (m1 - order) * (m2 - order)
+        cell = torch.empty(n, dtype=torch.int32, device="cuda")
+        assert self.lib.asvgp_kron_cell_index(self.X.data_ptr(), n, *self._mesh_args(False), cell.data_ptr(), None) == 0
+        perm = torch.argsort(cell, stable=True)
+        self.start = torch.zeros(ncell + 1, dtype=torch.int64, device="cuda")
+        self.start[1:] = torch.cumsum(torch.bincount(cell, minlength=ncell), 0)
+        dt = torch.float32 if self._fp32_storage else torch.float64
+        self.Xs, self.ys, self.ws = self.X[perm].to(dt).contiguous(), self.y[perm].to(dt).contiguous(), None if w is None else self.w[perm].contiguous()
+
+    def _mesh_args(self, with_m=True):
+        return tuple(v for i in (0, 1) for v in (self.mesh[i].data_ptr(), self.mesh[i].shape[0], self.delta[i]) + ((self.m[i],) if with_m else ()))
+
+    def phi_pass(self, sorted_cells=True):
+        L, n = self.lib, self.X.shape[0]
+        tail = self._mesh_args() + (self.order, self._stats.data_ptr()) + (() if self.w is None else (self._wstats.data_ptr(),)) + (None,)
+        if sorted_cells:
+            entry = (L.asvgp_phi_accumulate_kron2d_sorted_weighted if self.w is not None else
+                     L.asvgp_phi_accumulate_kron2d_sorted_f32 if self._fp32_storage else L.asvgp_phi_accumulate_kron2d_sorted)
+            data = (self.Xs.data_ptr(), self.ys.data_ptr()) + (() if self.w is None else (self.ws.data_ptr(),)) + (n, self.start.data_ptr())
+        else:
+            entry = L.asvgp_phi_accumulate_kron2d_weighted if self.w is not None else L.asvgp_phi_accumulate_kron2d
+            data = (self.X.data_ptr(), self.y.data_ptr()) + (() if self.w is None else (self.w.data_ptr(),)) + (n,)
+        assert entry(*data, *tail) == 0, L.asvgp_last_error_string()
+        torch.cuda.synchronize()
+
+
+# (order, m1, m2, N, cell-sorted forms too, what the plan must say of the shape)
+KRON_PHI_PLAN_CASES = [
+    (1, 2, 3, 5, True, "one strip"),                   # 2 x 3 mesh points: 2 cells in one strip of 8, most waves idle
+    (3, 12, 10, 4001, True, "strips fit"),             # the everyday path, a ragged last chunk
+    (1, 66, 66, 3000, True, "strip loop wraps"),       # 529 strips on 512 workgroups; 4225 cells padded to 4232
+    (1, 5, 5, 4096 * 256 + 1, False, "point clamp"),   # per point only: 4097 workgroups' worth of points on 4096
+    (3, 285, 285, 5000, True, "gather clamp"),         # 8250 workgroups' worth of gather outputs on 8192; 97 MB of staging, freed at once
+]
+
+
+@pytest.mark.parametrize("order,m1,m2,N,sorted_too,what", KRON_PHI_PLAN_CASES)
+def test_kron_phi_launch_plan_names_the_branch_that_runs(A, order, m1, m2, N, sorted_too, what):
+    """The branches of the Kronecker Phi pass's launch plan (csrc/kron_phi_launch.hpp): asvgp_kron_phi_launch_plan_host names the branch
+    for each shape, then the real entries run through GPR_kron - plain fp64, fp32 storage and weighted (weights with zeros); the
+    cell-sorted statistics are the per-point ones to 1e-12 of the largest entry with the same zero pattern, the per-point ones the
+    oracle's to the same 1e-12, the weight sums numpy's to 1e-12."""
+    from asvgp_amd import _lib
+    lib = _lib.get_lib()
+    env = (int(os.environ.get("ASVGP_KRON_PHI_ATOMICS", "0")) != 0, int(os.environ.get("ASVGP_KRON_PHI_GRID", "512")))
+
+    def plan(sorted_, weighted, f32):
+        p = np.full(12, -99, dtype=np.int64)
+        assert lib.asvgp_kron_phi_launch_plan_host(sorted_, weighted, f32, N, m1, m2, m1 - order + 1, m2 - order + 1, order, env[0], env[1], 1,
+                                                   p.ctypes.data) == 0, lib.asvgp_last_error_string()
+        return dict(zip(("status", "kernel", "grid", "threads", "gather_grid", "staging", "ncell", "ncell_pad", "clear_all"), (int(v) for v in p)))
+
+    for weighted in (0, 1):
+        p = plan(0, weighted, 0)
+        assert (p["kernel"], p["grid"], p["threads"], p["clear_all"]) == (1, min(-(-N // 256), 4096), 256, 1)
+        assert (what == "point clamp") == (-(-N // 256) > 4096)
+    if sorted_too and env == (False, 512):
+        strips = -(-(m1 - order) * (m2 - order) // 8)
+        outputs = (order * (2 * order + 1) + order + 2) * m1 * m2
+        for form in ((1, 0, 0), (1, 0, 1), (1, 1, 0)):
+            p = plan(*form)
+            assert (p["kernel"], p["grid"], p["threads"], p["clear_all"], p["ncell_pad"]) == (3, min(strips, 512), 512, 0, 8 * strips), (form, p)
+            assert p["gather_grid"] == min(-(-outputs // 256), 8192) and p["staging"] > 0
+        assert {"one strip": strips == 1, "strips fit": 1 < strips <= 512, "strip loop wraps": strips > 512,
+                "gather clamp": -(-outputs // 256) > 8192}[what]
+
+    rng = np.random.default_rng(order * 1000 + m1)
+    X32 = np.stack([rng.uniform(0.001, 0.999, N), rng.uniform(-0.999, 1.999, N)], axis=1).astype(np.float32)
+    y32 = (np.sin(6 * X32[:, :1]) * np.cos(2 * X32[:, 1:]) + 0.1 * rng.normal(size=(N, 1))).astype(np.float32)
+    X, y = X32.astype(np.float64), y32.astype(np.float64)                   # (fp32 values: all three models see the same data)
+    w = rng.choice([0.0, 1.5, 2.5, 4.0], size=N)                            # (every log w >= 0: their sum does not cancel)
+    B = getattr(A, "B%dSpline" % order)
+    if min(m1, m2) >= 3:
+        mk = lambda data, **kw: A.GPR_kron(data, [A.Matern12(), A.Matern12()], [B(0, 1, m1), B(-1, 2, m2)], **kw)
+    else:
+        mk = lambda data, weights=None: _BareKronPhi(order, m1, m2, data[0], data[1], weights)
+    models = [("fp64", mk((torch.from_numpy(X), torch.from_numpy(y))), None)]
+    if sorted_too:
+        models.append(("fp32 storage", mk((torch.from_numpy(X32), torch.from_numpy(y32))), None))
+    models.append(("weighted", mk((torch.from_numpy(X), torch.from_numpy(y)), weights=w), w))
+    refs = {}
+    for tag, model, wt in models:
+        assert model._fp32_storage == (tag == "fp32 storage")
+        stats = {}
+        for sorted_cells in ((True, False) if sorted_too else (False,)):
+            model._stats.fill_(7.0)
+            if wt is not None:
+                model._wstats.fill_(7.0)
+            model.phi_pass(sorted_cells=sorted_cells)
+            stats[sorted_cells] = model._stats.clone()
+            if wt is not None:
+                ws = model._wstats.cpu().numpy()
+                sums = (wt.sum(), np.log(wt[wt > 0]).sum(), float((wt > 0).sum()))
+                assert all(abs(g - r) <= 1e-12 * abs(r) for g, r in zip(ws, sums)), (tag, sorted_cells, ws, sums)
+        s_point = stats[False]
+        sc = s_point.abs().max().item()
+        if sorted_too:
+            assert (stats[True] - s_point).abs().max().item() <= 1e-12 * sc, tag
+            assert torch.equal(stats[True] == 0, s_point == 0), tag
+        key = wt is not None
+        if key not in refs:
+            refs[key] = _oracle_kron_statistics(order, m1, m2, X, y, wt)
+        nb, got = model.noff * model.Mtot, s_point.cpu().numpy()
+        for part in (slice(0, nb), slice(nb, nb + model.Mtot), slice(nb + model.Mtot, None)):       # block band, Kuf y, y^T y: each against its own largest
+            assert np.max(np.abs(got[part] - refs[key][part])) <= 1e-12 * np.max(np.abs(refs[key][part])), (tag, part)
+
+
 def test_gpmodel_surface_on_every_model_class(A):
     """trainable_variables / predict_y / predict_log_density (the GPflow GPModel methods the scripts call) exist on all three
     model classes and agree with the posterior moments."""
